@@ -7,7 +7,11 @@ steps over RCCL. A step = label map/p_hat + forward + fused loss + backward +
 update (+ the averaging round when t % I == 0). value = images/s of the whole
 job (all ranks), timed over exactly --steps steps between barriers.
 
-Other BASELINE configs, as sub-records of the same line:
+A plain run (``python bench.py --gpus N --steps K --warmup W``) sets up, warms up and times that
+step only, and prints the headline record (``value``, ``ms_per_step``, the update kernel's
+``roofline``). ``--dump-outputs DIR`` also writes what the last timed step left (dump_outputs).
+
+With ``--full``, the other BASELINE configs as sub-records of the same line:
   configs[2]  the averaging-period sweep I in {1, 8, 16, 32} of the same step (``period_sweep``)
               and one timed CoDA round (``coda_round``: the RCCL all-reduce + finalise, xGMI share)
   configs[0]  ResNet-18 b32 224^2 I=8 on the GPUs (``configs0.gpu``) next to the reference CPU
@@ -15,7 +19,7 @@ Other BASELINE configs, as sub-records of the same line:
   configs[3]  exact AUC of 2^24 scores at 1 % positives (``auc_eval``)
   configs[4]  exact AUC of 2^27 scores at 0.1 % positives (``auc_eval_extreme``), with the C
               oracle's counts on the full vector in its cpu_baseline
-plus the loss kernel at a streaming size (``surrogate_kernel``).
+plus the loss kernel at a streaming size (``surrogate_kernel``) and the step's ``step_roofline``.
 
 Launch: ``python bench.py --gpus N`` with no launcher starts N rank processes itself (a
 torch.distributed.run child, before this process touches the GPU) and exits with its code;
@@ -27,7 +31,7 @@ Kernel timing: HIP events recorded on the stream each kernel is launched on
 launch inside the timed region. roofline.achieved = algorithmic bytes per launch
 / average launch duration.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -44,9 +48,26 @@ from pathlib import Path
 
 REPO = Path(__file__).resolve().parent
 sys.path.insert(0, str(REPO))
-from distributedauc_amd import use_tuned_miopen_db  # noqa: E402
+from distributedauc_amd import MIOPEN_DB, use_tuned_miopen_db  # noqa: E402
 
-use_tuned_miopen_db()  # before any convolution: the shipped MI355X find/perf db
+
+def scratch_miopen_db() -> str:
+    """The shipped MI355X find/perf db through a scratch copy, unless MIOPEN_USER_DB_PATH is given:
+    MIOpen appends the find results of shapes the db lacks (the --full legs' ResNet-18 and eval-mode
+    convolutions) to its user db, and the committed files must stay as they are. Rank processes and
+    CPU workers inherit the variable; the process that made the copy removes it when it exits."""
+    if "MIOPEN_USER_DB_PATH" not in os.environ:
+        import atexit
+        import shutil
+
+        db = tempfile.mkdtemp(prefix="dauc_miopen_db_")
+        shutil.copytree(MIOPEN_DB, db, dirs_exist_ok=True)
+        atexit.register(lambda pid=os.getpid(): os.getpid() == pid and shutil.rmtree(db, ignore_errors=True))
+        os.environ["MIOPEN_USER_DB_PATH"] = db
+    return use_tuned_miopen_db()
+
+
+scratch_miopen_db()  # before any convolution
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -70,6 +91,13 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also run every other leg (period sweep, coda_round, in-training evaluation, configs[0], "
+                        "the exact-AUC and loss-kernel legs, step_roofline, CPU baselines); without it only the "
+                        "headline training step is set up, warmed up and timed")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one left (loss, a/b/alpha, p_hat, a fixed seeded "
+                        "sample of the parameters and of their running average) as DIR/<name>.npy")
     p.add_argument("--arch", default="resnet50")
     p.add_argument("--batch", type=int, default=256)
     p.add_argument("--image-size", type=int, default=224)
@@ -142,6 +170,14 @@ def parse(argv=None):
     p.add_argument("--cw-threads", type=int, default=1, help=argparse.SUPPRESS)
     p.add_argument("--cw-out", default="", help=argparse.SUPPRESS)
     return p.parse_args(argv)
+
+
+def headline_only(args):
+    """A run without --full: every leg but the headline training step is switched off."""
+    args.sweep_I = ""
+    args.eval_images = args.r18_steps = args.bn_steps = 0
+    args.no_auc = args.no_surrogate = args.no_cpu_baseline = True
+    return args
 
 
 _last_log = ["start", time.time()]
@@ -410,6 +446,8 @@ def bench_train(args, world, rank, device):
     upd.enabled = sur.enabled = False
     upd.restore()
     sur.restore()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(coda, args.dump_outputs)
     loss = float(coda.last_loss.item())
     out = {
         "dt": dt, "imgs": world * args.batch * args.steps, "loss": loss, "n_params": coda.state.numel(),
@@ -420,13 +458,33 @@ def bench_train(args, world, rank, device):
     }
     if args.sweep_I:
         out["period_sweep"] = bench_period_sweep(coda, it, args, world)
-    if grouped():
+    if grouped() and args.full:
         out["coda_round"] = bench_coda_round(coda, world)
     if args.eval_images > 0:
         out["training_eval"] = bench_training_eval(coda, args, world, rank, device)
     del coda, it
     torch.cuda.empty_cache()
     return out
+
+
+def dump_outputs(coda, out_dir, sample=1 << 20):
+    """What the last timed step left with its caller, as <out_dir>/<name>.npy (fp32): the step's loss,
+    (a, b, alpha), p_hat, and the parameters and their running average at `sample` positions of the
+    flat buffer (sorted, drawn once from a fixed seed, so two builds write the same positions; all of
+    them when the model is smaller), with the positions themselves in sample_index.npy (fp64).
+    16 MiB in all at the default sample."""
+    torch.cuda.synchronize()
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    st = coda.state
+    n = st.params.numel()
+    idx = np.arange(n) if n <= sample else np.sort(np.random.default_rng(20240607).choice(n, sample, replace=False))
+    sel = torch.from_numpy(idx).to(st.params.device)
+    arrays = {"loss": coda.last_loss.reshape(1), "abalpha": st.abalpha, "p_hat": st.p_hat,
+              "params_sample": st.params[sel], "avg_sample": st.avg[sel]}
+    for name, t in arrays.items():
+        np.save(d / f"{name}.npy", t.detach().float().cpu().numpy())
+    np.save(d / "sample_index.npy", idx.astype(np.float64))
 
 
 def bench_period_sweep(coda, it, args, world):
@@ -1169,6 +1227,8 @@ def gemm_selections(path: str) -> None:
 
 def main():
     args = parse()
+    if not args.full:
+        headline_only(args)
     if args.cpu_coda_worker:
         cpu_coda_worker(args)
         return
@@ -1258,7 +1318,7 @@ def main():
                              "achieved": upd_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": upd_gbs / HBM_PEAK_GBS, "traffic": load_traffic("pd_update"),
                              "bytes_per_launch": res["update_bytes"], "avg_launch_us": res["update_ms"] * 1e3},
-                "step_roofline": step_roofline(args, res),
+                "step_roofline": step_roofline(args, res) if args.full else None,
                 "surrogate_us_per_call": res["surrogate_us"],
                 "step_graph": {"replayed": res["graph"], "captures": res["graph_captures"],
                                "what": "label map -> forward -> surrogate -> backward replayed from one HIP graph; "

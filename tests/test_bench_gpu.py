@@ -21,8 +21,8 @@ def test_bench_self_launches_two_ranks():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--backend", "gloo", "--no-train",
-                        "--no-surrogate", "--no-cpu-baseline", "--auc-log2n", "18", "--auc2-log2n", "0",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
+                        "--no-train", "--no-surrogate", "--no-cpu-baseline", "--auc-log2n", "18", "--auc2-log2n", "0",
                         "--auc-reps", "1"], env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -43,7 +43,7 @@ def test_bench_full_two_ranks_gloo(tmp_path):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--backend", "gloo",
+    cmd = [sys.executable, str(REPO / "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
            "--arch", "resnet18", "--batch", "32", "--image-size", "64", "--steps", "4", "--warmup", "2",
            "--sweep-I", "1,2", "--sweep-steps", "2", "--eval-images", "256", "--r18-steps", "8",
            "--auc-log2n", "20", "--auc2-log2n", "21", "--auc-reps", "1", "--auc-shard-min", "0", "--sur-log2b", "16", "--sur-reps", "5",
@@ -83,8 +83,8 @@ def test_bench_default_sizes_two_ranks_gloo(tmp_path):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "3",
-           "--sweep-I", "1,8,16", "--sweep-steps", "16", "--eval-images", "1024", "--r18-steps", "8", "--auc-reps", "1",
+    cmd = [sys.executable, str(REPO / "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "4",
+           "--warmup", "3", "--sweep-I", "1,8,16", "--sweep-steps", "16", "--eval-images", "1024", "--r18-steps", "8", "--auc-reps", "1",
            "--sur-reps", "10"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560)
     (tmp_path / "stderr.log").write_text(r.stderr)
@@ -106,6 +106,40 @@ def test_bench_default_sizes_two_ranks_gloo(tmp_path):
         assert out[k]["P"] == P  # the bench's synthetic_scores at 2^24 @ 1 % and 2^27 @ 0.1 %
     assert out["step_roofline"]["flop_per_step"] > 6e12 and out["step_roofline"]["bn"]["bytes_per_step"] > 0
     assert out["cpu_baseline"] is None and "N = 1 only" in out["cpu_baseline_note"]
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) at reduced sizes: the headline record with exactly --steps timed steps and
+    none of the other legs, and --dump-outputs' arrays (fp32 / fp64, finite, within the size limit)."""
+    import numpy as np
+
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--arch", "resnet18", "--batch", "32",
+                        "--image-size", "64", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)],
+                       env=env, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-3000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["value"] > 0 and out["unit"] == "imgs/sec"
+    assert abs(out["value"] - 32 / (out["ms_per_step"] / 1e3)) <= 1e-6 * out["value"]
+    assert out["higher_is_better"] is True and out["dtype"] == "bf16"
+    for k in ("period_sweep", "training_eval", "configs0", "auc_eval", "auc_eval_extreme", "surrogate_kernel"):
+        assert k not in out, k
+    arrays = {f.stem: np.load(f) for f in d.glob("*.npy")}
+    assert set(arrays) == {"loss", "abalpha", "p_hat", "params_sample", "avg_sample", "sample_index"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    n = out["config"]["params"]  # ResNet-18 with 2 classes: larger than the sample
+    idx = arrays["sample_index"]  # positions in the flat buffer (its tensors start at aligned offsets)
+    assert arrays["params_sample"].shape == arrays["avg_sample"].shape == idx.shape == (1 << 20,) and n > 1 << 20
+    assert (np.diff(idx) >= 1).all() and idx[0] >= 0 and (idx == np.floor(idx)).all()
+    assert np.abs(arrays["params_sample"]).max() > 0
+    assert arrays["loss"].shape == (1,) and arrays["loss"][0] == np.float32(out["final_loss"])
+    assert arrays["abalpha"].shape == (3,) and sum(f.stat().st_size for f in d.glob("*.npy")) <= 64_000_000
 
 
 @pytest.mark.timeout(300)

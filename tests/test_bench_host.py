@@ -34,6 +34,19 @@ def test_defaults_cover_the_baseline_configs():
     assert a.r18_steps > 0 and a.cpu_workers == 4                                     # configs[0]
 
 
+def test_plain_run_keeps_the_headline_leg_only():
+    """Without --full every leg but the headline training step is off; --full leaves the defaults."""
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    b.headline_only(a)
+    assert not a.no_train and a.no_auc and a.no_surrogate and a.no_cpu_baseline
+    assert (a.sweep_I, a.eval_images, a.r18_steps, a.bn_steps) == ("", 0, 0, 0)
+    assert (a.steps, a.warmup, a.arch, a.batch, a.I) == (7, 2, "resnet50", 256, 16)
+    f = b.parse(["--full", "--dump-outputs", "d"])
+    assert f.full and f.dump_outputs == "d" and f.sweep_I and not f.no_auc
+
+
 def test_world_size_mismatch_fails_before_touching_the_gpu():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "4", "--no-train", "--no-auc",

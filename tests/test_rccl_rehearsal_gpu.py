@@ -7,7 +7,7 @@ the fp64 alpha all-reduce, the two-step sharded exact AUC's uint8 slot and int64
 at configs[3] and configs[4] sizes (counts vs the C oracle), the pair-count record gather, the
 split evaluation's broadcasts and score all-gather, a barrier and a HIP-graph capture after the
 communicator exists (bit-identical to eager, and the reference trajectory within 1e-5). The bench
-runs the same group with `--gpus 1 --backend nccl` (test below)."""
+runs the same group with `--full --gpus 1 --backend nccl` (test below)."""
 from __future__ import annotations
 
 import json
@@ -68,9 +68,9 @@ def test_rccl_rehearsal_one_rank(tmp_path):
 
 @pytest.mark.timeout(600)
 def test_bench_nccl_one_rank(tmp_path):
-    """bench.py --gpus 1 --backend nccl: the whole bench on a one-rank RCCL group (torch.distributed.run
+    """bench.py --full --gpus 1 --backend nccl: the whole bench on a one-rank RCCL group (torch.distributed.run
     child, world > 1 code paths), reduced sizes: the line reports the nccl group and a coda_round."""
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--backend", "nccl",
+    cmd = [sys.executable, str(REPO / "bench.py"), "--full", "--gpus", "1", "--backend", "nccl",
            "--arch", "resnet18", "--batch", "32", "--image-size", "64", "--steps", "4", "--warmup", "2",
            "--sweep-I", "1,2", "--sweep-steps", "2", "--eval-images", "256", "--r18-steps", "8",
            "--auc-log2n", "20", "--auc2-log2n", "21", "--auc-reps", "1", "--auc-shard-min", "0",
