@@ -20,7 +20,7 @@
 
 #include <type_traits>
 
-#include "count_index.h"
+#include "auc_eval_internal.h"
 
 namespace dauc {
 namespace {
@@ -890,19 +890,9 @@ int dauc_split_scores(const float* scores, const void* labels, int label_dtype, 
         (reinterpret_cast<uintptr_t>(workspace) & 7u))
         return DAUC_EINVAL;
     hipStream_t st = as_hip(stream);
-    switch (label_dtype) {
-        case DAUC_LABEL_I8:
-            return launch_split(scores, static_cast<const int8_t*>(labels), n, pos_out, neg_out,
-                                stats, workspace, st);
-        case DAUC_LABEL_I32:
-            return launch_split(scores, static_cast<const int32_t*>(labels), n, pos_out, neg_out,
-                                stats, workspace, st);
-        case DAUC_LABEL_I64:
-            return launch_split(scores, static_cast<const int64_t*>(labels), n, pos_out, neg_out,
-                                stats, workspace, st);
-        default:
-            return DAUC_EINVAL;
-    }
+    return with_labels(labels, label_dtype, [&](auto* lab) {
+        return launch_split(scores, lab, n, pos_out, neg_out, stats, workspace, st);
+    });
 }
 
 size_t dauc_compact_workspace_size(int64_t n) { return compact_ws_bytes(n < 0 ? 0 : n); }
@@ -919,19 +909,9 @@ int compact_positives_zeroing(const float* scores, const void* labels, int label
         workspace == nullptr || workspace_bytes < dauc_compact_workspace_size(n) ||
         (reinterpret_cast<uintptr_t>(workspace) & 15u) || (reinterpret_cast<uintptr_t>(stats) & 7u))
         return DAUC_EINVAL;
-    switch (label_dtype) {
-        case DAUC_LABEL_I8:
-            return launch_compact(scores, static_cast<const int8_t*>(labels), n, pos_out, stats, workspace, st, zero3,
-                                  zero_w, nzero_w);
-        case DAUC_LABEL_I32:
-            return launch_compact(scores, static_cast<const int32_t*>(labels), n, pos_out, stats, workspace, st, zero3,
-                                  zero_w, nzero_w);
-        case DAUC_LABEL_I64:
-            return launch_compact(scores, static_cast<const int64_t*>(labels), n, pos_out, stats, workspace, st, zero3,
-                                  zero_w, nzero_w);
-        default:
-            return DAUC_EINVAL;
-    }
+    return with_labels(labels, label_dtype, [&](auto* lab) {
+        return launch_compact(scores, lab, n, pos_out, stats, workspace, st, zero3, zero_w, nzero_w);
+    });
 }
 
 int compact_unordered(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out,
@@ -1071,12 +1051,7 @@ int compact_unordered(const float* scores, const void* labels, int label_dtype, 
                                nfill, nblk);
         return launch_status();
     };
-    switch (label_dtype) {
-        case DAUC_LABEL_I8: return go(static_cast<const int8_t*>(labels));
-        case DAUC_LABEL_I32: return go(static_cast<const int32_t*>(labels));
-        case DAUC_LABEL_I64: return go(static_cast<const int64_t*>(labels));
-        default: return DAUC_EINVAL;
-    }
+    return with_labels(labels, label_dtype, go);
 }
 }  // namespace dauc
 

@@ -8,7 +8,7 @@
 //   2. the one-pass positive compaction: labels read once, the positives' scores gathered (in no
 //      particular order), P counted on the device, their top-bucket histogram built;
 //   3. the count index built straight from the unsorted positives, sized by the device's P
-//      (auc_sort.hip, direct_*: the grids are sized for the index's capacity and loop), and the
+//      (count_index.hip, direct_*: the grids are sized for the index's capacity and loop), and the
 //      labeled query pass over the scores [part * n / parts, (part + 1) * n / parts), which also
 //      counts the non-finite queried scores (sklearn rejects them, _ranking.py:868-869) and writes
 //      the verdict: 1 = counted, 2 = the index cannot hold this table (more than 219,838
@@ -27,12 +27,10 @@
 #include <hip/hip_runtime.h>
 
 #include "dauc.h"
-#include "count_index.h"
+#include "auc_eval_internal.h"
 
 namespace dauc {
 namespace {
-
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 // workspace header (bytes): [0, 24) W, T, #non-finite queried scores (u64, the query's atomics);
 // [24, 56) the compaction's counters: P, tag (0), #non-finite positives, #labels outside {-1, 1};
@@ -55,10 +53,13 @@ struct EvalWs {
     void* tws;                    // sort + tree + count-index workspace (a table of at most n/2 keys)
     size_t sws_bytes, tws_bytes;
     unsigned* stab;               // the two-step evaluation's cell-slotted table (+inf filled by step 1)
+    size_t bytes;                 // the whole workspace
 };
 
+// the one description of the workspace: the pointers, and on a null base the size (sort_workspace.h)
 EvalWs eval_ws(void* ws, int64_t n) {
-    char* p = static_cast<char*>(ws);
+    WsWalker k(ws);
+    char* p = k.take<char>(kHdr);
     EvalWs w;
     w.wt = reinterpret_cast<unsigned long long*>(p);
     w.slot = reinterpret_cast<unsigned long long*>(p + 24);
@@ -66,32 +67,24 @@ EvalWs eval_ws(void* ws, int64_t n) {
     w.spare = reinterpret_cast<unsigned long long*>(p + 64);
     w.split_stats = reinterpret_cast<int64_t*>(p + 128);
     w.hist = reinterpret_cast<unsigned*>(p + kHistOff);
-    p += kHdr;
-    w.pos = reinterpret_cast<float*>(p);
-    p += align256(size_t(n) * 4);
-    w.neg = reinterpret_cast<float*>(p);
-    p += align256(size_t(n / 2 + 1) * 4);
+    w.pos = k.take<float>(n);
+    w.neg = k.take<float>(n / 2 + 1);
     w.sws_bytes = dauc_split_workspace_size(n);
-    w.sws = p;
-    p += align256(w.sws_bytes);
+    w.sws = k.take<char>(w.sws_bytes);
     w.tws_bytes = dauc_sort_workspace_size(n / 2 + 1);
-    w.tws = p;
-    p += align256(w.tws_bytes);
-    w.stab = reinterpret_cast<unsigned*>(p);
+    w.tws = k.take<char>(w.tws_bytes);
+    w.stab = k.take<unsigned>(slotted_table_bytes(direct_capacity(n)) / 4);
+    w.bytes = k.used();
     return w;
 }
 
-size_t eval_ws_bytes(int64_t n) {
-    return kHdr + align256(size_t(n) * 4) + align256(size_t(n / 2 + 1) * 4) + align256(dauc_split_workspace_size(n)) +
-           align256(dauc_sort_workspace_size(n / 2 + 1)) + align256(slotted_table_bytes(direct_capacity(n)));
-}
+size_t eval_ws_bytes(int64_t n) { return eval_ws(nullptr, n).bytes; }
 
 bool valid_args(const float* scores, const void* labels, int label_dtype, int64_t n, int part, int parts,
                 void* workspace, size_t workspace_bytes) {
     return n > 0 && scores != nullptr && labels != nullptr && workspace != nullptr &&
            workspace_bytes >= eval_ws_bytes(n) && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0 &&
-           parts >= 1 && part >= 0 && part < parts &&
-           (label_dtype == DAUC_LABEL_I8 || label_dtype == DAUC_LABEL_I32 || label_dtype == DAUC_LABEL_I64);
+           parts >= 1 && part >= 0 && part < parts && label_dtype_ok(label_dtype);
 }
 
 // [a, a + an) and [b, b + bn) overlap (byte ranges)
@@ -269,7 +262,12 @@ int64_t slot_cap(int parts) {
     return fair + fair / 4 + 64;
 }
 
-size_t slot_bytes(int parts) { return kSlotHdr + align256(size_t(slot_cap(parts)) * 4); }
+size_t slot_bytes(int parts) {  // the header and histogram, then the scores
+    WsWalker k(nullptr);
+    k.take<char>(kSlotHdr);
+    k.take<float>(slot_cap(parts));
+    return k.used();
+}
 
 // the slice of the labels rank `part` compacts: boundaries on 256-label multiples (int8 label
 // loads stay 16-byte aligned for every slice of an aligned array)

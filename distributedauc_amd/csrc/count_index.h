@@ -1,5 +1,5 @@
-// The count index of the positive table (auc_sort.hip builds it and counts the queries through
-// it). gfx950 only.
+// The count index of the positive table (count_index.hip and auc_sort.hip build it,
+// count_query.hip counts the queries through it). gfx950 only.
 //
 // Keys: an fp32 score maps to a uint32 that orders like the float, with -0 and +0 on one key
 // (fp32 equality semantics). The table's keys are split into CELLS by arithmetic on the key:
@@ -23,7 +23,13 @@ namespace dauc {
 
 constexpr unsigned kPadKey = 0xffffffffu;  // above every finite score's key (max 0xff7fffff)
 
-// the order-preserving key (-0 -> +0 by adding +0)
+__device__ __forceinline__ unsigned key_of(float f) {
+    if (f == 0.0f) f = 0.0f;  // -0 -> +0
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// the same key (-0 -> +0 by adding +0)
 __device__ __forceinline__ unsigned key_fast(float f) {
     const unsigned u = __float_as_uint(f + 0.0f);
     return u ^ (static_cast<unsigned>(static_cast<int>(u) >> 31) | 0x80000000u);
@@ -140,7 +146,7 @@ struct LabelWords<int8_t> {
 };
 
 // The two-step sharded evaluation's gathered slots (auc_eval.hip), read in place by the direct
-// build (auc_sort.hip, direct_count_slots_kernel): slot r at slots + r * sbytes holds a header of
+// build (count_index.hip, direct_count_slots_kernel): slot r at slots + r * sbytes holds a header of
 // u64 words {P_r, 0, #non-finite positives, #labels outside {-1, 1}, n}, the
 // top-bucket histogram of its positives (kCiTop u32) at hist_off and at most cap scores at
 // data_off. The build's first workgroup also writes the record of the part it serves.
@@ -156,7 +162,7 @@ struct SlotSource {
 };
 constexpr int kMaxSlotParts = 1024;
 
-// The count index built straight from the unsorted positives (auc_sort.hip, build_direct_index):
+// The count index built straight from the unsorted positives (count_index.hip, build_direct_index):
 // device pointers into the caller's sort workspace.
 struct DirectIndex {
     const unsigned* table;  // [M + 16] cell-ordered keys, +inf padded

@@ -97,95 +97,21 @@ __device__ __forceinline__ bool arrive_last(unsigned* counter, unsigned nblocks,
     return *lds_flag != 0;
 }
 
-// auc_count.hip: dauc_compact_positives that also zeroes zero3[0..3) and zero_w[0..nzero_w)
-// (used by auc_eval.hip)
-int compact_positives_zeroing(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out,
-                              int64_t* stats, void* workspace, size_t workspace_bytes, unsigned long long* zero3,
-                              hipStream_t st, unsigned* zero_w = nullptr, int nzero_w = 0);
+// ---- label arrays ---------------------------------------------------------------------------
+// The element types a label array may have (dauc.h, DAUC_LABEL_*). with_labels calls f with the
+// typed pointer and returns its status, or DAUC_EINVAL for any other dtype.
+inline bool label_dtype_ok(int label_dtype) {
+    return label_dtype == DAUC_LABEL_I8 || label_dtype == DAUC_LABEL_I32 || label_dtype == DAUC_LABEL_I64;
+}
 
-// auc_count.hip: the one-call evaluation's single-pass, unordered positive compaction. stats[0]
-// (P), stats[2] (non-finite positives), stats[3] (labels outside {-1, 1}) must be zero on entry
-// and stats[1] must hold `tag` (else no tile reserves or writes anything); block 0 zeroes
-// zero_next[0, 2, 3], sets zero_next[1] = next_tag, and zeroes zero3[0..3) (nullable); the grid
-// zeroes zero_w[0..nzero_w). At most `cap` positives are stored (stats[0] still counts them all).
-// hist_out (nullable; kCiTop words, zero on entry) += the top-bucket histogram of the positives'
-// keys (count_index.h), so a build from them can skip its histogram pass. *put = put_val (put
-// nullable; block 0).
-int compact_unordered(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out,
-                      unsigned long long* stats, unsigned long long tag, unsigned long long* zero_next,
-                      unsigned long long next_tag, unsigned long long* zero3, unsigned* zero_w, int nzero_w,
-                      hipStream_t st, int64_t cap = INT64_MAX, unsigned* hist_out = nullptr,
-                      unsigned long long* put = nullptr, unsigned long long put_val = 0ull,
-                      unsigned* fill_w = nullptr, int64_t nfill16 = 0);
-
-// auc_sort.hip: the count index built straight from the unsorted positives (no radix sort, no
-// tree) and the labeled query pass over scores [begin, end); the table is ordered by cell only.
-// The table size M is read from the device (*Mp, the compaction's count), so nothing waits for the
-// host; the workspace is carved for Mcap = direct_capacity(n) keys. Without a ready histogram
-// the build's own `hist` (kCiTop words at direct_hist_offset(Mcap)) must be zero on entry; with
-// one (the table's top-bucket histogram, whose total is the table size), the per-cell counters
-// (direct_cnt_ptr) must be. *verdict (device) = 1 when the count index held the table, 2 when the
-// caller must run the sorted path (M > Mcap, or a skewed table).
-bool direct_enabled();  // the search mode is automatic (always, except in a tuning build's mode 1 / 2)
-int64_t direct_capacity(int64_t n);
-int64_t direct_hist_offset(int64_t Mcap);  // byte offset of `hist` in the sort workspace
-// the per-cell counters the count pass adds into (zeroed by the histogram pass, or by the caller
-// when it hands over a ready histogram)
-unsigned* direct_cnt_ptr(void* workspace, int64_t Mcap);
-int64_t direct_cnt_words();
-struct DirectIndex;  // count_index.h
-// the direct build alone (4 launches; 3 with a ready histogram: `ready_hist` (kCiTop words, or
-// nullptr) already holds the table's top-bucket histogram and the per-cell counters are zero):
-// fills *ix with the index's device pointers
-int build_direct_index(const float* pos, const unsigned long long* Mp, int64_t Mcap, void* workspace,
-                       size_t workspace_bytes, hipStream_t st, DirectIndex* ix, const unsigned* ready_hist = nullptr);
-// check (nullable, one u32; the two-step evaluation's consistency word): += #queried scores
-// (labels != 1) over [begin, end), mod 2^32 -- counted by the query pass whether or not the index
-// held the table.
-int counts_labeled_direct(const float* pos, const unsigned long long* Mp, int64_t Mcap, const float* scores,
-                          const void* labels, int label_dtype, int64_t begin, int64_t end,
-                          unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                          void* workspace, size_t workspace_bytes, hipStream_t st,
-                          const unsigned* ready_hist = nullptr, unsigned* check = nullptr);
-
-// the two-step evaluation's build + query straight from the gathered slots (no gather copy):
-// the count pass reads the slots in place (and writes the part's record header, count_index.h
-// SlotSource), then blocks, scatter and the labeled query over [begin, end) as above. The per-cell
-// counters must be zero on entry (dauc_auc_eval_compact_part zeroes them; a build leaves them
-// zero again).
-struct SlotSource;
-int counts_labeled_direct_slots(const SlotSource& src, float* pos, int64_t Mcap, const float* scores,
-                                const void* labels, int label_dtype, int64_t begin, int64_t end,
-                                unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                                void* workspace, size_t workspace_bytes, hipStream_t st, unsigned* check);
-
-// the cell-slotted form of the same (round 6; the two-step evaluation's default): one count pass
-// inserts every key into its cell's 8-word slot of `stab` (filled with +inf, and the packed byte
-// counters and meta's skew word zeroed, by the compaction of step 1), then the query pass, which
-// builds the block words from the byte counts itself: two launches instead of four.
-int64_t slotted_cells(int64_t Mcap);
-size_t slotted_table_bytes(int64_t Mcap);   // primary + secondary + tertiary regions (count_index.h)
-size_t slotted_fill_bytes(int64_t Mcap);    // the +inf part: primary + secondary
-int64_t slotted_cnt_words();                // the packed byte counters (words) the compaction zeroes
-unsigned* slotted_meta_ptr(void* workspace, int64_t Mcap);
-// the one-call evaluation's slotted form: the same insertion from the compacted positives `pos`
-// (P on the device at *Mp, the top-bucket histogram ready), then the query pass (two launches
-// instead of three after the compaction)
-int counts_labeled_direct_slotted(const float* pos, const unsigned long long* Mp, int64_t Mcap, unsigned* stab,
-                                  const float* scores, const void* labels, int label_dtype, int64_t begin,
-                                  int64_t end, unsigned long long* wins_ties, unsigned long long* nonfinite,
-                                  unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
-                                  const unsigned* ready_hist);
-int counts_labeled_slotted(const SlotSource& src, unsigned* stab, int64_t Mcap, const float* scores,
-                           const void* labels, int label_dtype, int64_t begin, int64_t end,
-                           unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                           void* workspace, size_t workspace_bytes, hipStream_t st, unsigned* check);
-// dauc_auc_counts_sorted_labeled with the count index optional: the evaluation's sorted path runs
-// only after the count index refused the table (verdict 2), and the sorted table has the same keys
-// and the same plan, so it skips that build (count_index = false) and goes to the distinct-key
-// index or the tree at once
-int counts_sorted_labeled(const float* pos, int64_t P, const float* scores, const void* labels, int label_dtype,
-                          int64_t begin, int64_t end, unsigned long long* wins_ties, unsigned long long* nonfinite,
-                          void* workspace, size_t workspace_bytes, hipStream_t st, bool count_index);
+template <typename F>
+int with_labels(const void* labels, int label_dtype, F&& f) {
+    switch (label_dtype) {
+        case DAUC_LABEL_I8: return f(static_cast<const int8_t*>(labels));
+        case DAUC_LABEL_I32: return f(static_cast<const int32_t*>(labels));
+        case DAUC_LABEL_I64: return f(static_cast<const int64_t*>(labels));
+        default: return DAUC_EINVAL;
+    }
+}
 
 }  // namespace dauc

@@ -349,7 +349,7 @@ __global__ __launch_bounds__(kThreads) void surrogate_kernel(
 //
 // A grid-stride (persistent) loop walks the batch with a large stride, so concurrently open
 // DRAM pages are far apart (measured: 6.2 TB/s for this 5:4 read:write mix vs 6.5 TB/s for
-// one chunk per workgroup, scripts/probe_stream.hip). Here every workgroup takes ONE
+// one chunk per workgroup, a stand-alone streaming probe). Here every workgroup takes ONE
 // contiguous chunk of 256 x 4 x S elements (the dispatcher hands chunks out roughly in
 // address order, like the update kernel's one-shot grid) and issues all of its loads
 // before any math; every WAVE reduces its 6 partials with DPP (no barrier, no LDS), the dF/dh
@@ -884,22 +884,10 @@ int dispatch_labels(const float* h, int64_t hs, const void* y, int yt, int64_t B
                     double* out64, float* grad3, float* loss, double* sums4, int accumulate,
                     void* ws, size_t ws_bytes, hipStream_t st, int variant = 0) {
     if (variant != 0 && yt != DAUC_LABEL_I8) return DAUC_EINVAL;
-    switch (yt) {
-        case DAUC_LABEL_I8:
-            return launch_surrogate<CLASS_ONLY>(h, hs, static_cast<const int8_t*>(y), B, abalpha,
-                                                p_hat, dh, dhs, out64, grad3, loss, sums4,
-                                                accumulate, ws, ws_bytes, st, variant);
-        case DAUC_LABEL_I32:
-            return launch_surrogate<CLASS_ONLY>(h, hs, static_cast<const int32_t*>(y), B, abalpha,
-                                                p_hat, dh, dhs, out64, grad3, loss, sums4,
-                                                accumulate, ws, ws_bytes, st);
-        case DAUC_LABEL_I64:
-            return launch_surrogate<CLASS_ONLY>(h, hs, static_cast<const int64_t*>(y), B, abalpha,
-                                                p_hat, dh, dhs, out64, grad3, loss, sums4,
-                                                accumulate, ws, ws_bytes, st);
-        default:
-            return DAUC_EINVAL;
-    }
+    return with_labels(y, yt, [&](auto* lab) {  // (variant is 0 for every dtype but int8)
+        return launch_surrogate<CLASS_ONLY>(h, hs, lab, B, abalpha, p_hat, dh, dhs, out64, grad3, loss, sums4,
+                                            accumulate, ws, ws_bytes, st, variant);
+    });
 }
 
 template <bool CLASS_ONLY, typename ZT, typename YT>
@@ -924,21 +912,10 @@ template <bool CLASS_ONLY, typename ZT>
 int launch_logits_y(const ZT* z, int64_t ldz, const void* y, int yt, int64_t B, const float* abalpha,
                     const float* p_hat, ZT* dz, int64_t lddz, float* h_out, double* out64, float* grad3,
                     float* loss, double* sums4, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
-    switch (yt) {
-        case DAUC_LABEL_I8:
-            return launch_logits_t<CLASS_ONLY>(z, ldz, static_cast<const int8_t*>(y), B, abalpha, p_hat, dz, lddz,
-                                               h_out, out64, grad3, loss, sums4, accumulate, ws, ws_bytes, st);
-        case DAUC_LABEL_I32:
-            return launch_logits_t<CLASS_ONLY>(z, ldz, static_cast<const int32_t*>(y), B, abalpha, p_hat, dz,
-                                               lddz, h_out, out64, grad3, loss, sums4, accumulate, ws, ws_bytes,
-                                               st);
-        case DAUC_LABEL_I64:
-            return launch_logits_t<CLASS_ONLY>(z, ldz, static_cast<const int64_t*>(y), B, abalpha, p_hat, dz,
-                                               lddz, h_out, out64, grad3, loss, sums4, accumulate, ws, ws_bytes,
-                                               st);
-        default:
-            return DAUC_EINVAL;
-    }
+    return with_labels(y, yt, [&](auto* lab) {
+        return launch_logits_t<CLASS_ONLY>(z, ldz, lab, B, abalpha, p_hat, dz, lddz, h_out, out64, grad3, loss, sums4,
+                                           accumulate, ws, ws_bytes, st);
+    });
 }
 
 template <bool CLASS_ONLY>

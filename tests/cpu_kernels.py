@@ -168,7 +168,7 @@ def auc_eval_enqueue(scores, labels, part, parts, out=None):
     return rec
 
 
-_INDEX_CAP = 219_838  # 3 / 2 x the count index's cells (auc_sort.hip direct_capacity)
+_INDEX_CAP = 219_838  # 3 / 2 x the count index's cells (count_index.hip direct_capacity)
 
 
 def _slot_cap(parts):

@@ -67,6 +67,36 @@ def test_workspace_sizes():
     assert L.dauc_split_workspace_size(1 << 24) >= (1 << 24) // 8192 * 20  # 8192-score tiles
 
 
+_SIZE_NS = (1, 2047, 2048, 2049, 1 << 20, (1 << 24) + 1, 1 << 27)
+# Recorded from the library (host arithmetic only). The sort and evaluation workspaces are 768 bytes
+# below what they were while size and carve were written apart (sort: 1115136, 1131008, 1131008,
+# 1132544, 10030592, 143795200, 1142553600; evaluation: 1255680, 1406208, 1406976, 1407232,
+# 21256704, 182548480, 1386858240): that size added 256-byte terms no region used.
+_SIZES = {
+    "dauc_sort_workspace_size": (1114368, 1130240, 1130240, 1131776, 10029824, 143794432, 1142552832),
+    "dauc_auc_eval_workspace_size": (1254912, 1405440, 1406208, 1406464, 21255936, 182547712, 1386857472),
+    "dauc_split_workspace_size": (84, 84, 84, 84, 2624, 41044, 327744),
+}
+_SLOT_BYTES = {1: 1107968, 2: 558336, 8: 146176}  # dauc_auc_slot_bytes(n, parts): the same for every n
+
+
+def test_workspace_size_functions_are_pinned():
+    """The four size functions at the sizes where a sort tile (2048 keys), a distinct-key tile and
+    the large evaluations sit: non-decreasing in n, whole 256-byte regions where the layout is made
+    of them, and equal to the recorded values (a layout change shows here before it shows as an
+    out-of-bounds write on a GPU)."""
+    L = _lib.load()
+    for name, want in _SIZES.items():
+        got = tuple(int(getattr(L, name)(n)) for n in _SIZE_NS)
+        assert list(got) == sorted(got), (name, got)
+        if name != "dauc_split_workspace_size":
+            assert all(g % 256 == 0 for g in got), (name, got)
+        assert got == want, (name, got)
+    for parts, want in _SLOT_BYTES.items():
+        got = tuple(int(L.dauc_auc_slot_bytes(n, parts)) for n in _SIZE_NS)
+        assert got == (want,) * len(_SIZE_NS) and want % 256 == 0, (parts, got)
+
+
 def test_invalid_arguments_return_einval():
     L = _lib.load()
     null = ctypes.c_void_p(0)

@@ -1,14 +1,16 @@
-"""The search structures of the sort method (auc_sort.hip; dauc_set_search_mode of the tuning build,
-include/dauc_tuning.h) vs the C oracle.
+"""The search structures of the sort method (auc_sort.hip, count_index.hip, count_query.hip;
+dauc_set_search_mode of the tuning build, include/dauc_tuning.h) vs the C oracle.
 
 The labeled query pass (dauc_auc_counts_sorted_labeled, and through it dauc_auc_eval_counts)
 locates every negative among the sorted positives through one of: the count index (mode 0, the
 default where it fits: top 11 key bits -> bucket, multiply-high -> cell, per-8-cell LDS words of
-base + nibble counts, one 16-byte window for non-empty cells; the device falls back to the tree
-for skewed tables) or the LDS search tree (mode 1). Every case here runs in both modes, so the
-skewed cases also cover mode 0's device-side fallback. (Round 2's 16-key-slot cell index, a
-measured and slower alternative, was removed in round 4.) Bar: the integers (W, T) bit-exact against oracle/auc_oracle.c (sklearn's
-_binary_clf_curve counts, main.py:79-81) on the same scores.
+base + nibble counts, one 16-byte window for non-empty cells; for a table it cannot hold -- more
+than 1.5 keys per cell, or a cell of 15+ keys -- the device falls back to the distinct-key index
+where that holds the table, else to the tree), the LDS search tree (mode 1), or the LDS
+distinct-key index with the tree behind it (mode 2). Every case here runs in modes 0 and 1, so the
+skewed cases also cover mode 0's device-side fallback; the tile-boundary case runs all three.
+Bar: the integers (W, T) bit-exact against oracle/auc_oracle.c (sklearn's _binary_clf_curve counts,
+main.py:79-81) on the same scores.
 """
 from __future__ import annotations
 
@@ -102,10 +104,10 @@ def test_cells_signed_wide_and_special_values(dev, ops):
 
 
 def test_cells_ties_and_overflowing_cells(dev, ops):
-    """Quantised scores: runs of equal keys longer than a 16-key slot (the slot-cell pass
-    searches the rest of the cell in global memory; the count index finds a cell of 15+ keys
-    and keeps the tree), and a run of 20 equal keys in one cell with the rest of the table
-    uniform, ties across cell edges."""
+    """Quantised scores: runs of equal keys longer than a cell's nibble can count (the count
+    index finds a cell of 15+ keys and leaves the table to the distinct-key index or the tree),
+    and a run of 20 equal keys in one cell with the rest of the table uniform, ties across cell
+    edges."""
     rng = np.random.default_rng(3)
     n = 1 << 20
     for levels, p in ((3001, 0.01), (97, 0.05), (5, 0.2), (1, 0.01)):
@@ -125,7 +127,8 @@ def test_cells_ties_and_overflowing_cells(dev, ops):
 
 def test_cells_clustered_table(dev, ops):
     """90 % of the positives inside a 1e-4-wide interval: the cells of their top bucket hold
-    hundreds of keys each (slot + binary search in the cell pass)."""
+    hundreds of keys each (the count index marks the table skewed on the device; the
+    distinct-key index or the tree counts it)."""
     rng = np.random.default_rng(4)
     n = 1 << 20
     s = rng.random(n, dtype=np.float32)
@@ -151,10 +154,49 @@ def test_cells_label_types_and_ranges(dev, ops, ldtype):
         _check(ops, dev, s, y, begin, end, what=(begin, end))
 
 
+TILE_N = 20_011
+TILE_PS = (1, 1023, 1024, 1025, 2047, 2048, 2049, 4097)
+TILE_RANGES = ((0, TILE_N), (3, TILE_N - 5))
+
+
+@pytest.fixture(scope="module")
+def tile_cases():
+    """One score vector and, per table size, the positives' places and the oracle's (W, T) over
+    both query ranges -- computed once for the three label dtypes."""
+    rng = np.random.default_rng(20_011)
+    s = rng.random(TILE_N, dtype=np.float32)
+    cases = []
+    for P in TILE_PS:
+        y = -np.ones(TILE_N, np.int8)
+        y[rng.choice(TILE_N, P, replace=False)] = 1
+        cases.append((P, y, {r: _oracle_slice(s, y, *r) for r in TILE_RANGES}))
+    return s, cases
+
+
+@pytest.mark.parametrize("ldtype", [np.int8, np.int32, np.int64])
+def test_cells_tile_boundaries(dev, ops, tile_cases, ldtype):
+    """Tables of 1 .. 4097 positives inside 20,011 scores: one key, and one below / at / one past
+    a distinct-key tile (1024 keys), a sort tile (2048) and two sort tiles -- the sizes at which a
+    tile's tail, or a workspace region carved a region too early, first shows. Every search mode
+    (count index, tree, distinct-key index), every label dtype, the whole range and an unaligned
+    one; no non-finite score is counted."""
+    s, cases = tile_cases
+    ts = T(s, dev)
+    for P, y, refs in cases:
+        ty, tpos = T(y.astype(ldtype), dev), T(s[y == 1], dev)
+        for m in (0, 1, 2):
+            ops.set_search_mode(m)
+            for (begin, end), ref in refs.items():
+                wt = torch.zeros(3, dtype=torch.int64, device=dev)
+                ops.auc_counts_sorted_labeled(tpos, ts, ty, begin, end, wt, nonfinite=wt[2:])
+                assert tuple(wt[:2].cpu().tolist()) == ref, (P, m, begin, end)
+                assert int(wt[2]) == 0, (P, m, begin, end)
+
+
 def test_cells_table_size_limits(dev, ops):
-    """Table sizes around the limits: the count index up to 1.5 keys per cell (215,040 uses it,
-    400,000 is past it: the tree), the slot-cell index up to 16 keys per cell (573,440) and one
-    key past it (the tree in every mode)."""
+    """Table sizes around the count index's limit of 1.5 keys per cell (219,838 keys at most):
+    215,040 and 215,041 are within it, 400,000 and the two larger tables are past it and have far
+    more than 14,000 distinct keys, so the tree counts them in every mode."""
     rng = np.random.default_rng(6)
     n = 1 << 22
     for P in (215_040, 215_041, 400_000, 573_440, 573_441):
@@ -203,7 +245,7 @@ def test_search_mode_rejects_unknown(dev, ops):
 @pytest.mark.parametrize("fault", [1, 2, 3])
 def test_direct_build_guards_bad_indices(dev, ops, fault):
     """The direct count-index build checks every cell index and counter before its scatter stores
-    (auc_sort.hip, direct_scatter_kernel): the tuning build corrupts one key's cell (past the last
+    (count_index.hip, direct_scatter_kernel): the tuning build corrupts one key's cell (past the last
     cell / moved to the next cell) or one cell's counter between the count and scatter passes, and
     the evaluation reports verdict 2 -- the blocking call then takes the sorted path and returns
     the oracle's exact counts. Without the fault the same data is counted by the index (verdict 1)."""
