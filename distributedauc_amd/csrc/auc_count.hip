@@ -535,18 +535,14 @@ __global__ __launch_bounds__(kCmpThreads) void compact_write_kernel(
 // reservation counter), stats[2] (non-finite positives) and stats[3] (labels outside {-1, 1})
 // must be zero on entry; stats[1] is not written (N = n - P). Block 0 zeroes `zero_next` (the
 // next call's stats) and zero3[0..3); the grid zeroes the first `nzero_w` words of `zero_w`.
-// SLOTS groups of 16 labels per thread: 8 (a 32768-label tile) for small inputs; 32 (131072) for
-// large ones, where the reservation atomics of 4096 tiles on one address serialise (2^27 labels:
-// 65 us at 8 slots). HIST: hist_out += the top-bucket histogram of the positives' keys (an LDS
-// histogram per tile, its used buckets added once). Block 0 writes put_val to *put (nullable: the
+// A tile is THREADS x 16 x SLOTS labels (SLOTS groups of 16 labels per thread); the launcher
+// (compact_unordered, below) picks one of three shapes by n. HIST: hist_out += the top-bucket
+// histogram of the positives' keys (an LDS histogram per tile, its used buckets added once).
+// HIST is only instantiated true (both evaluations hand the histogram to the index build).
+// Block 0 writes put_val to *put (nullable: the
 // two-step evaluation's slot header length word). fill_w (nullable): the grid also fills nfill16
 // 16-byte words there with all-ones (the two-step's slotted table: +inf keys), by extra workgroups
 // past the tiles (blockIdx.x >= ntiles), which do only that and the zeroing.
-#ifdef DAUC_TUNING
-// tuning builds: DAUC_CMP_ABL = 1, a timing ablation of the tiles' reservation (WRONG output): every
-// tile writes from position 0 without its returning atomic on the one counter
-__device__ int g_cmp_abl = 0;
-#endif
 template <typename LT, int SLOTS, int THREADS = kCmpThreads, bool HIST = false>
 __global__ __launch_bounds__(THREADS) void compact_unordered_kernel(
     const float* __restrict__ s, const LT* __restrict__ lab, int64_t n, int vec, float* __restrict__ pos_out,
@@ -640,10 +636,6 @@ __global__ __launch_bounds__(THREADS) void compact_unordered_kernel(
 #pragma unroll
         for (int w = 0; w < kW; ++w) other += wtot[1][w];
         if (other) atomicAdd(stats + 3, static_cast<unsigned long long>(other));
-#ifdef DAUC_TUNING
-        if (g_cmp_abl == 1) base_s = 0ull;
-        else
-#endif
         base_s = tile ? atomicAdd(stats + 0, static_cast<unsigned long long>(tile)) : 0ull;
     }
     __syncthreads();
@@ -914,144 +906,54 @@ int compact_positives_zeroing(const float* scores, const void* labels, int label
     });
 }
 
-int compact_unordered(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out,
-                      unsigned long long* stats, unsigned long long tag, unsigned long long* zero_next,
-                      unsigned long long next_tag, unsigned long long* zero3, unsigned* zero_w, int nzero_w,
-                      hipStream_t st, int64_t cap, unsigned* hist_out, unsigned long long* put,
-                      unsigned long long put_val, unsigned* fill_w, int64_t nfill16) {
-    if (n <= 0 || scores == nullptr || labels == nullptr || pos_out == nullptr || stats == nullptr ||
-        zero_next == nullptr)
-        return DAUC_EINVAL;
-    const bool wide = n >= (int64_t(1) << 25);
-    // wide inputs: 1024-thread workgroups of 32 label groups per thread (524,288-label tiles: 256
-    // reservations at 2^27 instead of 1024 on the one counter address) -- 256
-    constexpr int kWideThreads = 256;
-    int slots = wide ? 32 : kCmpSlots;
-#ifdef DAUC_TUNING
-    // tuning builds: DAUC_CMP_SLOTS (8, 16, 32, 64) = label groups per thread whatever n
-    if (const char* e = getenv("DAUC_CMP_SLOTS");
-        e && (atoi(e) == 8 || atoi(e) == 16 || atoi(e) == 32 || atoi(e) == 64))
-        slots = atoi(e);
-#endif
-    // round 6: 512-thread tiles (8 groups per thread, the histogram form) from 2^23 labels below the
-    // wide shape: half the tiles, so half the reservations on the one counter, which serialise
-    // (the two-step's 2^24-label slice: 512 -> 256 tiles, step 1 17.9 -> 14.9 us; the one-call
-    // evaluation of 2^24 labels 114.9 -> 110.1 us; the 2^21-label slice keeps 256: 12.2 vs 12.8 us)
-    constexpr int kMidThreads = 512;
-    const bool mid_ok = !wide && hist_out != nullptr && slots == kCmpSlots;
-    int threads = wide ? kWideThreads : mid_ok && n >= (int64_t(1) << 23) ? kMidThreads : kCmpThreads;
-#ifdef DAUC_TUNING
-    // tuning builds: DAUC_CMP_THREADS (256, 512, 1024) = threads per tile of that form whatever n
-    if (const char* e = getenv("DAUC_CMP_THREADS");
-        mid_ok && e && (atoi(e) == 256 || atoi(e) == 512 || atoi(e) == 1024))
-        threads = atoi(e);
-#endif
-#ifdef DAUC_TUNING
-    {
-        static int abl = -1;
-        if (abl < 0) {
-            const char* e = getenv("DAUC_CMP_ABL");
-            abl = e ? atoi(e) : 0;
-            if (hipMemcpyToSymbol(HIP_SYMBOL(g_cmp_abl), &abl, sizeof(int)) != hipSuccess) return DAUC_EINVAL;
-        }
-    }
-#endif
-    const int64_t tile = int64_t(threads) * 16 * slots;
-    const int64_t nblk = (n + tile - 1) / tile;
-    if (nblk > 0x7fffffffLL) return DAUC_EINVAL;
-    const int vec = (reinterpret_cast<uintptr_t>(labels) & 15u) == 0;
-    // fill-only workgroups past the tiles: `per` 16-byte stores per thread (the tiles' CUs stay theirs)
-#ifdef DAUC_TUNING
-    static int per = 0;  // tuning builds: DAUC_FILL_PER_THREAD
-    if (per == 0) {
-        const char* e = getenv("DAUC_FILL_PER_THREAD");
-        per = e ? atoi(e) : 4;
-        if (per < 1 || per > 4096) per = 4;
-    }
-#else
+// The one launch of compact_unordered_kernel<LT, SLOTS, THREADS, HIST = true>: a tile is
+// THREADS x 16 x SLOTS labels; `per` 16-byte stores per thread in the fill-only workgroups past
+// the tiles (the tiles' CUs stay theirs). The kernel's tag / next_tag are 0: the evaluations keep
+// no state between calls, so stats[1] is the zero the caller wrote.
+template <typename LT, int SLOTS, int THREADS>
+static int launch_compact_unordered(const float* scores, const LT* lab, int64_t n, float* pos_out, int64_t cap,
+                             unsigned long long* stats, unsigned long long* zero_next, unsigned* hist_out,
+                             const CompactSide& side, hipStream_t st) {
     constexpr int per = 4;
-#endif
-    const int64_t nfill = fill_w != nullptr ? nfill16 : 0;
-    const int64_t extra = (nfill + int64_t(threads) * per - 1) / (int64_t(threads) * per);
+    constexpr int64_t tile = int64_t(THREADS) * 16 * SLOTS;
+    const int64_t nblk = (n + tile - 1) / tile;
+    const int64_t nfill = side.fill_w != nullptr ? side.nfill16 : 0;
+    const int64_t extra = (nfill + int64_t(THREADS) * per - 1) / (int64_t(THREADS) * per);
     if (nblk + extra > 0x7fffffffLL) return DAUC_EINVAL;
-    const dim3 grid(static_cast<unsigned>(nblk + extra)), block(threads);
-    uint4* fw = reinterpret_cast<uint4*>(fill_w);
-    auto go = [&](auto* lab) {
+    const int vec = (reinterpret_cast<uintptr_t>(lab) & 15u) == 0;
+    hipLaunchKernelGGL((compact_unordered_kernel<LT, SLOTS, THREADS, true>), dim3(static_cast<unsigned>(nblk + extra)),
+                       dim3(THREADS), 0, st, scores, lab, n, vec, pos_out, stats, 0ull, zero_next, 0ull, side.zero3,
+                       side.zero_w, side.nzero_w, cap, hist_out, side.put, side.put_val,
+                       reinterpret_cast<uint4*>(side.fill_w), nfill, nblk);
+    return launch_status();
+}
+
+int compact_unordered(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out, int64_t cap,
+                      unsigned long long* stats, unsigned long long* zero_next, unsigned* hist_out,
+                      const CompactSide& side, hipStream_t st) {
+    if (n <= 0 || scores == nullptr || labels == nullptr || pos_out == nullptr || stats == nullptr ||
+        zero_next == nullptr || hist_out == nullptr)
+        return DAUC_EINVAL;
+    // The three shapes, by n (every tile reserves its range of pos_out with one returning atomic
+    // on the one counter address, and those serialise: larger inputs take larger tiles):
+    //   n >= 2^25         256 threads x 32 groups: 131,072-label tiles (2^27 labels: 1024
+    //                     reservations; 4096 of the small shape's took 65 us)
+    //   2^23 <= n < 2^25  512 threads x 8 groups: 65,536-label tiles. Round 6: half the small
+    //                     shape's tiles (the two-step's 2^24-label slice: 512 -> 256 tiles, step 1
+    //                     17.9 -> 14.9 us; the one-call evaluation of 2^24 labels 114.9 -> 110.1 us)
+    //   otherwise         256 threads x 8 groups: 32,768-label tiles (the 2^21-label slice keeps
+    //                     256 threads: 12.2 vs 12.8 us)
+    return with_labels(labels, label_dtype, [&](auto* lab) {
         using LT = std::remove_const_t<std::remove_pointer_t<decltype(lab)>>;
-        if (mid_ok && threads == kMidThreads) {
-            hipLaunchKernelGGL((compact_unordered_kernel<LT, kCmpSlots, kMidThreads, true>), grid, block, 0, st, scores,
-                               lab, n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap,
-                               hist_out, put, put_val, fw, nfill, nblk);
-            return launch_status();
-        }
-#ifdef DAUC_TUNING
-        if (mid_ok && threads == 1024) {
-            hipLaunchKernelGGL((compact_unordered_kernel<LT, kCmpSlots, 1024, true>), grid, block, 0, st, scores, lab,
-                               n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out,
-                               put, put_val, fw, nfill, nblk);
-            return launch_status();
-        }
-        if (slots == 64) {
-            if (hist_out != nullptr)
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, 64, kCmpThreads, true>), grid, block, 0, st, scores,
-                                   lab, n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap,
-                                   hist_out, put, put_val, fw, nfill, nblk);
-            else
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, 64, kCmpThreads>), grid, block, 0, st, scores, lab, n,
-                                   vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out,
-                                   put, put_val, fw, nfill, nblk);
-            return launch_status();
-        }
-        if (slots == 16) {
-            if (hist_out != nullptr)
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, 16, kCmpThreads, true>), grid, block, 0, st, scores,
-                                   lab, n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap,
-                                   hist_out, put, put_val, fw, nfill, nblk);
-            else
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, 16, kCmpThreads>), grid, block, 0, st, scores, lab, n,
-                                   vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out,
-                                   put, put_val, fw, nfill, nblk);
-            return launch_status();
-        }
-        if ((slots == 32) != wide) {  // the other of the two product shapes
-            if (slots == 32 && hist_out != nullptr)
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, 32, kWideThreads, true>), grid, block, 0, st, scores,
-                                   lab, n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap,
-                                   hist_out, put, put_val, fw, nfill, nblk);
-            else if (slots == 32)
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, 32, kWideThreads>), grid, block, 0, st, scores, lab, n,
-                                   vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out,
-                                   put, put_val, fw, nfill, nblk);
-            else if (hist_out != nullptr)
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, kCmpSlots, kCmpThreads, true>), grid, block, 0, st,
-                                   scores, lab, n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w,
-                                   cap, hist_out, put, put_val, fw, nfill, nblk);
-            else
-                hipLaunchKernelGGL((compact_unordered_kernel<LT, kCmpSlots>), grid, block, 0, st, scores, lab, n, vec,
-                                   pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out, put,
-                                   put_val, fw, nfill, nblk);
-            return launch_status();
-        }
-#endif
-        if (wide && hist_out != nullptr)
-            hipLaunchKernelGGL((compact_unordered_kernel<LT, 32, kWideThreads, true>), grid, block, 0, st, scores, lab,
-                               n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out, put, put_val, fw,
-                               nfill, nblk);
-        else if (wide)
-            hipLaunchKernelGGL((compact_unordered_kernel<LT, 32, kWideThreads>), grid, block, 0, st, scores, lab, n, vec,
-                               pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out, put, put_val, fw,
-                               nfill, nblk);
-        else if (hist_out != nullptr)
-            hipLaunchKernelGGL((compact_unordered_kernel<LT, kCmpSlots, kCmpThreads, true>), grid, block, 0, st, scores,
-                               lab, n, vec, pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap,
-                               hist_out, put, put_val, fw, nfill, nblk);
-        else
-            hipLaunchKernelGGL((compact_unordered_kernel<LT, kCmpSlots>), grid, block, 0, st, scores, lab, n, vec,
-                               pos_out, stats, tag, zero_next, next_tag, zero3, zero_w, nzero_w, cap, hist_out, put, put_val, fw,
-                               nfill, nblk);
-        return launch_status();
-    };
-    return with_labels(labels, label_dtype, go);
+        if (n >= (int64_t(1) << 25))
+            return launch_compact_unordered<LT, 32, 256>(scores, lab, n, pos_out, cap, stats, zero_next, hist_out, side,
+                                                         st);
+        if (n >= (int64_t(1) << 23))
+            return launch_compact_unordered<LT, kCmpSlots, 512>(scores, lab, n, pos_out, cap, stats, zero_next,
+                                                                hist_out, side, st);
+        return launch_compact_unordered<LT, kCmpSlots, kCmpThreads>(scores, lab, n, pos_out, cap, stats, zero_next,
+                                                                    hist_out, side, st);
+    });
 }
 }  // namespace dauc
 

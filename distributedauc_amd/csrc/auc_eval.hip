@@ -142,23 +142,23 @@ int enqueue(const float* scores, const void* labels, int label_dtype, int64_t n,
     const bool slot = g_index_form == 0;
     unsigned* cnt = direct_cnt_ptr(w.tws, mcap);
     auto* meta8 = reinterpret_cast<unsigned long long*>(slotted_meta_ptr(w.tws, mcap) + 8);
-    int rc = compact_unordered(scores, labels, label_dtype, n, w.pos, w.slot, 0ull, w.spare, 0ull,
-                               slot ? meta8 : nullptr, cnt,
-                               static_cast<int>(slot ? slotted_cnt_words() : direct_cnt_words()), st, INT64_MAX,
-                               w.hist, nullptr, 0ull, slot ? w.stab : nullptr,
-                               slot ? static_cast<int64_t>(slotted_fill_bytes(mcap) / 16) : 0);
+    CompactSide side;
+    side.zero_w = cnt, side.nzero_w = static_cast<int>(slot ? slotted_cnt_words() : direct_cnt_words());
+    if (slot) {
+        side.zero3 = meta8;
+        side.fill_w = w.stab, side.nfill16 = static_cast<int64_t>(slotted_fill_bytes(mcap) / 16);
+    }
+    int rc = compact_unordered(scores, labels, label_dtype, n, w.pos, INT64_MAX, w.slot, w.spare, w.hist, side, st);
     if (rc) return rc;
-    const int64_t qlo = n * part / parts, qhi = n * (part + 1) / parts;
-    if (qhi <= qlo) return DAUC_OK;  // an empty part: verdict 0, counts 0
+    const LabeledQueries q{scores, labels, label_dtype, n * part / parts, n * (part + 1) / parts, w.wt, w.wt + 2};
+    if (q.end <= q.begin) return DAUC_OK;  // an empty part: verdict 0, counts 0
     if (!direct_enabled()) {
         // a tuning build forcing another search structure: straight to the sorted path
         return -static_cast<int>(hipMemsetAsync(w.verdict, 2, 1, st));
     }
     if (slot)
-        return counts_labeled_direct_slotted(w.pos, w.slot, mcap, w.stab, scores, labels, label_dtype, qlo, qhi, w.wt,
-                                             w.wt + 2, w.verdict, w.tws, w.tws_bytes, st, w.hist);
-    return counts_labeled_direct(w.pos, w.slot, mcap, scores, labels, label_dtype, qlo, qhi, w.wt, w.wt + 2,
-                                 w.verdict, w.tws, w.tws_bytes, st, w.hist);
+        return counts_labeled_direct_slotted(w.pos, w.slot, mcap, w.stab, q, w.verdict, w.tws, w.tws_bytes, st, w.hist);
+    return counts_labeled_direct(w.pos, w.slot, mcap, q, w.verdict, w.tws, w.tws_bytes, st, w.hist);
 }
 
 // The sorted path for a verdict-2 evaluation (P, N known): counts of part `part` into w.wt.
@@ -169,11 +169,10 @@ int sorted_path(const float* scores, const void* labels, int label_dtype, int64_
     const dauc_stream_t ds = reinterpret_cast<dauc_stream_t>(st);
     if (P <= N) {
         // the positives are the table; every other score of the part is a query read in place
-        const int64_t qlo = n * part / parts, qhi = n * (part + 1) / parts;
-        if (qhi <= qlo) return DAUC_OK;
+        const LabeledQueries q{scores, labels, label_dtype, n * part / parts, n * (part + 1) / parts, w.wt, w.wt + 2};
+        if (q.end <= q.begin) return DAUC_OK;
         // (the count index refused this table: its plan over the sorted copy would too)
-        return counts_sorted_labeled(w.pos, P, scores, labels, label_dtype, qlo, qhi, w.wt, w.wt + 2, w.tws,
-                                     w.tws_bytes, st, false);
+        return counts_sorted_labeled(w.pos, P, q, w.tws, w.tws_bytes, st, false);
     }
     // the negatives are the smaller class: materialise both (the split also checks every score)
     int rc = dauc_split_scores(scores, labels, label_dtype, n, w.pos, w.neg, w.split_stats, w.sws, w.sws_bytes, ds);
@@ -381,11 +380,14 @@ int dauc_auc_eval_compact_part(const float* scores, const void* labels, int labe
         return DAUC_OK;
     }
     const size_t lsz = label_dtype == DAUC_LABEL_I8 ? 1 : label_dtype == DAUC_LABEL_I32 ? 4 : 8;
+    CompactSide side;
+    side.zero3 = meta8;
+    side.zero_w = cnt, side.nzero_w = static_cast<int>(ncnt);
+    side.put = hdr + kSlotN, side.put_val = static_cast<unsigned long long>(n);
+    side.fill_w = w.stab, side.nfill16 = static_cast<int64_t>(tab / 16);
     return compact_unordered(scores + lo, static_cast<const char*>(labels) + size_t(lo) * lsz, label_dtype, hi - lo,
-                             reinterpret_cast<float*>(static_cast<char*>(slot) + kSlotHdr), hdr, 0ull, w.spare, 0ull,
-                             meta8, cnt, static_cast<int>(ncnt), st, slot_cap(parts),
-                             reinterpret_cast<unsigned*>(static_cast<char*>(slot) + kSlotHist), hdr + kSlotN,
-                             static_cast<unsigned long long>(n), w.stab, static_cast<int64_t>(tab / 16));
+                             reinterpret_cast<float*>(static_cast<char*>(slot) + kSlotHdr), slot_cap(parts), hdr,
+                             w.spare, reinterpret_cast<unsigned*>(static_cast<char*>(slot) + kSlotHist), side, st);
 }
 
 int dauc_auc_eval_query_part(const float* scores, const void* labels, int label_dtype, int64_t n, int part, int parts,
@@ -403,19 +405,20 @@ int dauc_auc_eval_query_part(const float* scores, const void* labels, int label_
     hipStream_t st = as_hip(stream);
     const EvalWs w = with_record(eval_ws(workspace, n), part_out);
     const int64_t mcap = direct_capacity(n);
-    const int64_t qlo = query_lo(n, part, parts), qhi = query_hi(n, part, parts);
+    const LabeledQueries q{scores, labels, label_dtype, query_lo(n, part, parts), query_hi(n, part, parts), w.wt,
+                           w.wt + 2};
     // the build reads the gathered slots in place (no gather copy): its count pass sums their
     // headers and histograms, writes this part's record (counts zeroed, P, the check word, the
     // label counts) and m_eff (w.spare[0]: P, or past the index's capacity on an overflow); the
     // query pass brings the check word's low half back to zero
     SlotSource src{static_cast<const unsigned char*>(slots), slot_bytes(parts), kSlotHist, kSlotHdr, parts, part,
-                   slot_cap(parts), n, qhi - qlo, w.wt, w.slot, reinterpret_cast<unsigned long long*>(w.verdict),
+                   slot_cap(parts), n, q.end - q.begin, w.wt, w.slot, reinterpret_cast<unsigned long long*>(w.verdict),
                    w.spare};
     if (g_index_form == 1)
-        return counts_labeled_direct_slots(src, w.pos, mcap, scores, labels, label_dtype, qlo, qhi, w.wt, w.wt + 2,
-                                           w.verdict, w.tws, w.tws_bytes, st, reinterpret_cast<unsigned*>(part_out + 4));
-    return counts_labeled_slotted(src, w.stab, mcap, scores, labels, label_dtype, qlo, qhi, w.wt, w.wt + 2, w.verdict,
-                                  w.tws, w.tws_bytes, st, reinterpret_cast<unsigned*>(part_out + 4));
+        return counts_labeled_direct_slots(src, w.pos, mcap, q, w.verdict, w.tws, w.tws_bytes, st,
+                                           reinterpret_cast<unsigned*>(part_out + 4));
+    return counts_labeled_slotted(src, w.stab, mcap, q, w.verdict, w.tws, w.tws_bytes, st,
+                                  reinterpret_cast<unsigned*>(part_out + 4));
 }
 
 int dauc_auc_eval_query_part_sorted(const float* scores, const void* labels, int label_dtype, int64_t n, int part,
@@ -449,12 +452,10 @@ int dauc_auc_eval_query_part_sorted(const float* scores, const void* labels, int
         // this rank's own slice of the scores against the sorted table (the count index would refuse
         // it again: the distinct-key index for tie-heavy tables, else the tree); on a bad gather the
         // counts are discarded with the verdict
-        const int64_t qlo = slice_lo(n, part, parts), qhi = slice_lo(n, part + 1, parts);
         auto* rec = reinterpret_cast<unsigned long long*>(part_out);
-        if (qhi > qlo &&
-            (rc = counts_sorted_labeled(w.pos, P, scores, labels, label_dtype, qlo, qhi, rec, rec + 2, w.tws,
-                                        w.tws_bytes, st, false)))
-            return rc;
+        const LabeledQueries q{scores, labels, label_dtype, slice_lo(n, part, parts), slice_lo(n, part + 1, parts), rec,
+                               rec + 2};
+        if (q.end > q.begin && (rc = counts_sorted_labeled(w.pos, P, q, w.tws, w.tws_bytes, st, false))) return rc;
     }
     hipLaunchKernelGGL(sorted_part_verdict_kernel, dim3(1), dim3(64), 0, st, bad, P, part_out);
     return launch_status();

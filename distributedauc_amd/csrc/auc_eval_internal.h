@@ -9,26 +9,50 @@
 
 namespace dauc {
 
+// The labeled queries of one pass and where their counts go: every score of [begin, end) whose
+// label is not 1 is a query; wins_ties[0, 1] += (W, T), *nonfinite (nullable) += the non-finite
+// queried scores.
+struct LabeledQueries {
+    const float* scores;
+    const void* labels;
+    int label_dtype;
+    int64_t begin, end;
+    unsigned long long* wins_ties;
+    unsigned long long* nonfinite;
+
+    bool valid() const {
+        return begin >= 0 && end >= begin && wins_ties != nullptr &&
+               (end == begin || (scores != nullptr && labels != nullptr)) && label_dtype_ok(label_dtype);
+    }
+    bool empty() const { return end == begin; }
+};
+
 // auc_count.hip: dauc_compact_positives that also zeroes zero3[0..3) and zero_w[0..nzero_w)
 // (used by auc_eval.hip)
 int compact_positives_zeroing(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out,
                               int64_t* stats, void* workspace, size_t workspace_bytes, unsigned long long* zero3,
                               hipStream_t st, unsigned* zero_w = nullptr, int nzero_w = 0);
 
-// auc_count.hip: the one-call evaluation's single-pass, unordered positive compaction. stats[0]
-// (P), stats[2] (non-finite positives), stats[3] (labels outside {-1, 1}) must be zero on entry
-// and stats[1] must hold `tag` (else no tile reserves or writes anything); block 0 zeroes
-// zero_next[0, 2, 3], sets zero_next[1] = next_tag, and zeroes zero3[0..3) (nullable); the grid
-// zeroes zero_w[0..nzero_w). At most `cap` positives are stored (stats[0] still counts them all).
-// hist_out (nullable; kCiTop words, zero on entry) += the top-bucket histogram of the positives'
-// keys (count_index.h), so a build from them can skip its histogram pass. *put = put_val (put
-// nullable; block 0).
-int compact_unordered(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out,
-                      unsigned long long* stats, unsigned long long tag, unsigned long long* zero_next,
-                      unsigned long long next_tag, unsigned long long* zero3, unsigned* zero_w, int nzero_w,
-                      hipStream_t st, int64_t cap = INT64_MAX, unsigned* hist_out = nullptr,
-                      unsigned long long* put = nullptr, unsigned long long put_val = 0ull,
-                      unsigned* fill_w = nullptr, int64_t nfill16 = 0);
+// What the compaction's grid does on the side for the stages after it (every pointer nullable):
+struct CompactSide {
+    unsigned long long* zero3 = nullptr;  // block 0 zeroes zero3[0..3)
+    unsigned* zero_w = nullptr;           // the grid zeroes zero_w[0..nzero_w): a later build's per-cell counters
+    int nzero_w = 0;
+    unsigned long long* put = nullptr;    // block 0: *put = put_val (the two-step slot header's length word)
+    unsigned long long put_val = 0ull;
+    unsigned* fill_w = nullptr;           // the grid fills nfill16 16-byte words here with all-ones (the slotted
+    int64_t nfill16 = 0;                  // table's +inf keys), by extra workgroups past the tiles
+};
+
+// auc_count.hip: the evaluations' single-pass, unordered positive compaction. stats[0] (P),
+// stats[1], stats[2] (non-finite positives), stats[3] (labels outside {-1, 1}) must be zero on
+// entry (a non-zero stats[1]: no tile reserves or writes anything); block 0 zeroes
+// zero_next[0..4). At most `cap` positives are stored (stats[0] still counts them all). hist_out
+// (required; kCiTop words, zero on entry) += the top-bucket histogram of the positives' keys
+// (count_index.h), so a build from them can skip its histogram pass.
+int compact_unordered(const float* scores, const void* labels, int label_dtype, int64_t n, float* pos_out, int64_t cap,
+                      unsigned long long* stats, unsigned long long* zero_next, unsigned* hist_out,
+                      const CompactSide& side, hipStream_t st);
 
 // count_index.hip: the count index built straight from the unsorted positives (no radix sort, no
 // tree) and the labeled query pass over scores [begin, end); the table is ordered by cell only.
@@ -54,10 +78,8 @@ int build_direct_index(const float* pos, const unsigned long long* Mp, int64_t M
 // check (nullable, one u32; the two-step evaluation's consistency word): += #queried scores
 // (labels != 1) over [begin, end), mod 2^32 -- counted by the query pass whether or not the index
 // held the table.
-int counts_labeled_direct(const float* pos, const unsigned long long* Mp, int64_t Mcap, const float* scores,
-                          const void* labels, int label_dtype, int64_t begin, int64_t end,
-                          unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                          void* workspace, size_t workspace_bytes, hipStream_t st,
+int counts_labeled_direct(const float* pos, const unsigned long long* Mp, int64_t Mcap, const LabeledQueries& q,
+                          unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
                           const unsigned* ready_hist = nullptr, unsigned* check = nullptr);
 
 // the two-step evaluation's build + query straight from the gathered slots (no gather copy):
@@ -66,10 +88,9 @@ int counts_labeled_direct(const float* pos, const unsigned long long* Mp, int64_
 // counters must be zero on entry (dauc_auc_eval_compact_part zeroes them; a build leaves them
 // zero again).
 struct SlotSource;
-int counts_labeled_direct_slots(const SlotSource& src, float* pos, int64_t Mcap, const float* scores,
-                                const void* labels, int label_dtype, int64_t begin, int64_t end,
-                                unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                                void* workspace, size_t workspace_bytes, hipStream_t st, unsigned* check);
+int counts_labeled_direct_slots(const SlotSource& src, float* pos, int64_t Mcap, const LabeledQueries& q,
+                                unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
+                                unsigned* check);
 
 // the cell-slotted form of the same (round 6; the two-step evaluation's default): one count pass
 // inserts every key into its cell's 8-word slot of `stab` (filled with +inf, and the packed byte
@@ -84,21 +105,17 @@ unsigned* slotted_meta_ptr(void* workspace, int64_t Mcap);
 // (P on the device at *Mp, the top-bucket histogram ready), then the query pass (two launches
 // instead of three after the compaction)
 int counts_labeled_direct_slotted(const float* pos, const unsigned long long* Mp, int64_t Mcap, unsigned* stab,
-                                  const float* scores, const void* labels, int label_dtype, int64_t begin,
-                                  int64_t end, unsigned long long* wins_ties, unsigned long long* nonfinite,
-                                  unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
-                                  const unsigned* ready_hist);
-int counts_labeled_slotted(const SlotSource& src, unsigned* stab, int64_t Mcap, const float* scores,
-                           const void* labels, int label_dtype, int64_t begin, int64_t end,
-                           unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                           void* workspace, size_t workspace_bytes, hipStream_t st, unsigned* check);
+                                  const LabeledQueries& q, unsigned* verdict, void* workspace, size_t workspace_bytes,
+                                  hipStream_t st, const unsigned* ready_hist);
+int counts_labeled_slotted(const SlotSource& src, unsigned* stab, int64_t Mcap, const LabeledQueries& q,
+                           unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
+                           unsigned* check);
 // dauc_auc_counts_sorted_labeled with the count index optional: the evaluation's sorted path runs
 // only after the count index refused the table (verdict 2), and the sorted table has the same keys
 // and the same plan, so it skips that build (count_index = false) and goes to the distinct-key
 // index or the tree at once
-int counts_sorted_labeled(const float* pos, int64_t P, const float* scores, const void* labels, int label_dtype,
-                          int64_t begin, int64_t end, unsigned long long* wins_ties, unsigned long long* nonfinite,
-                          void* workspace, size_t workspace_bytes, hipStream_t st, bool count_index);
+int counts_sorted_labeled(const float* pos, int64_t P, const LabeledQueries& q, void* workspace,
+                          size_t workspace_bytes, hipStream_t st, bool count_index);
 
 // count_query.hip: the labeled query pass through the count index. The form says which build the
 // index came from, and with it which query_ci_kernel instantiation runs:
@@ -134,8 +151,7 @@ struct CiForm {
         return f;
     }
 };
-int launch_ci(const float* scores, const void* labels, int label_dtype, int64_t begin, int64_t end, const CountWs& cw,
-              const unsigned* table, int64_t M, unsigned long long* out, unsigned long long* nonfinite, hipStream_t st,
+int launch_ci(const LabeledQueries& q, const CountWs& cw, const unsigned* table, int64_t M, hipStream_t st,
               const CiForm& form);
 
 }  // namespace dauc

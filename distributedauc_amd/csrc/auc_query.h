@@ -2,8 +2,6 @@
 // auc_sort.hip, the count index's in count_query.hip): the workgroup size and the grid.
 #pragma once
 
-#include <stdlib.h>
-
 #include "dauc_internal.h"
 
 namespace dauc {
@@ -20,17 +18,7 @@ inline int query_grid(int64_t L) {
             cus = 256;
         }
     }
-#ifdef DAUC_TUNING
-    // tuning builds: DAUC_QUERY_QPT = the queries per thread the grid aims at (default 4)
-    static int qpt = 0;
-    if (qpt == 0) {
-        const char* e = getenv("DAUC_QUERY_QPT");
-        qpt = e ? atoi(e) : 4;
-        if (qpt < 1 || qpt > 1024) qpt = 4;
-    }
-#else
-    constexpr int qpt = 4;
-#endif
+    constexpr int qpt = 4;  // the queries per thread the grid aims at
     int64_t g = (L + int64_t(qpt) * kQueryThreads - 1) / (int64_t(qpt) * kQueryThreads);
     if (g > 1 * cus) g = 1 * cus;  // 1024-thread workgroups
     if (g < 1) g = 1;

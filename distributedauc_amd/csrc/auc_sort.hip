@@ -25,7 +25,6 @@
 // Entry points: dauc_auc_counts_sorted, dauc_auc_counts_sorted_labeled, and counts_sorted_labeled
 // for the evaluation's verdict-2 fallback (auc_eval.hip).
 
-#include <stdlib.h>
 #include <type_traits>
 
 #include "auc_eval_internal.h"
@@ -1196,27 +1195,28 @@ int launch_dk_plain(const float* q, int64_t L, const DkWs& dk, int64_t M, unsign
     return launch_status();
 }
 
+// (in both launchers `lab` is q.labels with its element type)
 template <typename LT>
-int launch_dk(const float* s, const LT* lab, int64_t begin, int64_t end, const unsigned* ci_meta, const DkWs& dk,
-              int64_t M, unsigned long long* out, unsigned long long* nonfinite, hipStream_t st) {
+int launch_dk(const LabeledQueries& q, const LT* lab, const unsigned* ci_meta, const DkWs& dk, int64_t M,
+              hipStream_t st) {
     // both layouts enqueued: the one the device's distinct count does not select returns at once
-    const dim3 grid(query_grid(end - begin));
-    hipLaunchKernelGGL((dk_query_kernel<LT, true>), grid, dim3(kQueryThreads), kDkQueryLdsSmall, st, s, lab, begin,
-                       end, ci_meta, dk, M, out, nonfinite);
-    hipLaunchKernelGGL((dk_query_kernel<LT, false>), grid, dim3(kQueryThreads), kDkQueryLds, st, s, lab, begin, end,
-                       ci_meta, dk, M, out, nonfinite);
+    const dim3 grid(query_grid(q.end - q.begin));
+    hipLaunchKernelGGL((dk_query_kernel<LT, true>), grid, dim3(kQueryThreads), kDkQueryLdsSmall, st, q.scores, lab,
+                       q.begin, q.end, ci_meta, dk, M, q.wins_ties, q.nonfinite);
+    hipLaunchKernelGGL((dk_query_kernel<LT, false>), grid, dim3(kQueryThreads), kDkQueryLds, st, q.scores, lab, q.begin,
+                       q.end, ci_meta, dk, M, q.wins_ties, q.nonfinite);
     return launch_status();
 }
 
 template <typename LT>
-int launch_labeled(int k, const float* s, const LT* lab, int64_t begin, int64_t end, const TreeNode* tree,
-                   const TreeGeom& g, const unsigned* sorted, int64_t M, unsigned long long* out, unsigned long long* nonfinite,
-                   const unsigned* meta, hipStream_t st, const unsigned* dk_meta = nullptr) {
-    const dim3 grid(query_grid(end - begin)), block(kQueryThreads);
+int launch_labeled(int k, const LabeledQueries& q, const LT* lab, const TreeNode* tree, const TreeGeom& g,
+                   const unsigned* sorted, int64_t M, const unsigned* meta, hipStream_t st,
+                   const unsigned* dk_meta = nullptr) {
+    const dim3 grid(query_grid(q.end - q.begin)), block(kQueryThreads);
     const size_t lds = size_t(g.nodes) * sizeof(TreeNode);
-#define DAUC_QL(KV)                                                                                              \
-    hipLaunchKernelGGL((query_labeled_kernel<KV, LT>), grid, block, lds, st, s, lab, begin, end, tree, g, k, \
-                       sorted, M, out, nonfinite, meta, dk_meta)
+#define DAUC_QL(KV)                                                                                                 \
+    hipLaunchKernelGGL((query_labeled_kernel<KV, LT>), grid, block, lds, st, q.scores, lab, q.begin, q.end, tree, g, \
+                       k, sorted, M, q.wins_ties, q.nonfinite, meta, dk_meta)
     switch (k) {
         case 1: DAUC_QL(1); break;
         case 2: DAUC_QL(2); break;
@@ -1257,13 +1257,10 @@ int prepare_table(const float* table, int64_t M, const SortWorkspace& ws, hipStr
 
 bool direct_enabled() { return g_search_mode == 0; }
 
-int counts_sorted_labeled(const float* pos, int64_t P, const float* scores, const void* labels, int label_dtype,
-                          int64_t begin, int64_t end, unsigned long long* wins_ties, unsigned long long* nonfinite,
-                          void* workspace, size_t workspace_bytes, hipStream_t st, bool count_index) {
-    if (P < 0 || begin < 0 || end < begin || wins_ties == nullptr || (P > 0 && pos == nullptr) ||
-        (end > begin && (scores == nullptr || labels == nullptr)) || !label_dtype_ok(label_dtype))
-        return DAUC_EINVAL;
-    if (P == 0 || end == begin) return DAUC_OK;
+int counts_sorted_labeled(const float* pos, int64_t P, const LabeledQueries& q, void* workspace,
+                          size_t workspace_bytes, hipStream_t st, bool count_index) {
+    if (!q.valid() || P < 0 || (P > 0 && pos == nullptr)) return DAUC_EINVAL;
+    if (P == 0 || q.empty()) return DAUC_OK;
     if (workspace == nullptr || workspace_bytes < dauc_sort_workspace_size(P) || P > 0xffffffffLL) return DAUC_EINVAL;
     const SortWorkspace ws = sort_workspace(workspace, P);
     const unsigned* sorted = nullptr;
@@ -1282,16 +1279,12 @@ int counts_sorted_labeled(const float* pos, int64_t P, const float* scores, cons
     if (count && (rc = prepare_count(sorted, P, nw, st))) return rc;
     const unsigned* meta = count ? nw.meta : nullptr;
     if (distinct && (rc = prepare_dk(sorted, P, meta, dk, st))) return rc;
-    rc = with_labels(labels, label_dtype, [&](auto* lab) {
-        return launch_labeled(k, scores, lab, begin, end, ws.tree, g, sorted, P, wins_ties, nonfinite, meta, st,
-                              distinct ? dk.meta : nullptr);
+    rc = with_labels(q.labels, q.label_dtype, [&](auto* lab) {
+        return launch_labeled(k, q, lab, ws.tree, g, sorted, P, meta, st, distinct ? dk.meta : nullptr);
     });
-    if (rc == DAUC_OK && count)
-        rc = launch_ci(scores, labels, label_dtype, begin, end, nw, sorted, P, wins_ties, nonfinite, st, CiForm::sorted());
+    if (rc == DAUC_OK && count) rc = launch_ci(q, nw, sorted, P, st, CiForm::sorted());
     if (rc == DAUC_OK && distinct)
-        rc = with_labels(labels, label_dtype, [&](auto* lab) {
-            return launch_dk(scores, lab, begin, end, meta, dk, P, wins_ties, nonfinite, st);
-        });
+        rc = with_labels(q.labels, q.label_dtype, [&](auto* lab) { return launch_dk(q, lab, meta, dk, P, st); });
     return rc;
 }
 
@@ -1347,8 +1340,8 @@ int dauc_auc_counts_sorted_labeled(const float* pos, int64_t P, const float* sco
                                    int label_dtype, int64_t begin, int64_t end, unsigned long long* wins_ties,
                                    unsigned long long* nonfinite, void* workspace, size_t workspace_bytes,
                                    dauc_stream_t stream) {
-    return counts_sorted_labeled(pos, P, scores, labels, label_dtype, begin, end, wins_ties, nonfinite, workspace,
-                                 workspace_bytes, as_hip(stream), true);
+    return counts_sorted_labeled(pos, P, LabeledQueries{scores, labels, label_dtype, begin, end, wins_ties, nonfinite},
+                                 workspace, workspace_bytes, as_hip(stream), true);
 }
 
 }  // extern "C"

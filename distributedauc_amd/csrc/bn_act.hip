@@ -26,8 +26,6 @@
 
 #include <hip/hip_bf16.h>
 
-#include <stdlib.h>
-
 #include <initializer_list>
 #include <type_traits>
 
@@ -37,34 +35,18 @@ namespace dauc {
 namespace {
 
 constexpr int kBnThreads = 256;
-constexpr int kDefaultPartThreads = 512;  // profiles/r01/ab_bn_threads.jsonl
+// threads per workgroup of the partial-sum passes (256 | 512 | 1024 are built; 512 is the one
+// launched, profiles/r01/ab_bn_threads.jsonl). With ~256 row blocks the grid is about one
+// workgroup per CU, so the workgroup size sets the bytes in flight per CU.
+constexpr int kDefaultPartThreads = 512;
 constexpr int kMaxRowBlocks = 2048;  // partial rows per channel (workspace bound)
 constexpr int kFinThreads = 1024;    // finalize: 64 row subsets x 16 channel quads
 constexpr int kFinSubsets = kFinThreads / 16;
 
-// target row blocks per launch (tuning knob DAUC_BN_ROWBLOCKS; 256 measured best on MI355X:
-// 256 and 512 tie on the ResNet-50 step, 1024 / 2048 lose to the longer finalize)
-int row_block_target() {
-    static int v = 0;
-    if (v == 0) {
-        const char* e = getenv("DAUC_BN_ROWBLOCKS");
-        int t = e ? atoi(e) : 256;
-        v = (t >= 1 && t <= kMaxRowBlocks) ? t : 256;
-    }
-    return v;
-}
-// threads per workgroup of the partial-sum passes (DAUC_BN_PART_THREADS: 256 | 512 | 1024). With
-// ~256 row blocks the grid is about one workgroup per CU, so the workgroup size sets the bytes
-// in flight per CU.
-int part_threads() {
-    static int v = 0;
-    if (v == 0) {
-        const char* e = getenv("DAUC_BN_PART_THREADS");
-        const int t = e ? atoi(e) : kDefaultPartThreads;
-        v = (t == 256 || t == 512 || t == 1024) ? t : kDefaultPartThreads;
-    }
-    return v;
-}
+// target row blocks per launch: 256 measured best on MI355X (256 and 512 tie on the ResNet-50
+// step, 1024 / 2048 lose to the longer finalize)
+constexpr int kRowBlockTarget = 256;
+static_assert(kRowBlockTarget >= 1 && kRowBlockTarget <= kMaxRowBlocks, "partial rows fit the workspace");
 constexpr int kUnroll = 8;          // row passes whose loads are in flight together
 constexpr int kApplyVecs = 4;       // 16-byte vectors per thread in the elementwise kernels
 
@@ -175,7 +157,7 @@ int make_geometry(int64_t M, int C, int elem_bytes, Geometry& g, int threads = k
     g.CT = g.TPR * g.N;
     g.ctiles = C / g.CT;
     g.RPB = threads / g.TPR;
-    int64_t target = (row_block_target() + g.ctiles - 1) / g.ctiles;
+    int64_t target = (kRowBlockTarget + g.ctiles - 1) / g.ctiles;
     const int64_t passes = (M + g.RPB - 1) / g.RPB;
     if (target > passes) target = passes;
     if (target < 1) target = 1;
@@ -596,7 +578,7 @@ int bn_forward_t(const T* x, int64_t M, int C, const T* res, int relu, const flo
                  float* running_mean, float* running_var, float momentum, float eps, T* y, unsigned char* mask,
                  float* save_mean, float* save_invstd, void* ws, size_t ws_bytes, hipStream_t st) {
     Geometry g;
-    const int th = part_threads();
+    const int th = kDefaultPartThreads;
     if (make_geometry(M, C, sizeof(T), g, th) != DAUC_OK) return DAUC_EINVAL;
     if (ws == nullptr || ws_bytes < ws_bytes_for(C) || !aligned16p(ws)) return DAUC_EINVAL;
     if ((running_mean == nullptr) != (running_var == nullptr)) return DAUC_EINVAL;
@@ -624,7 +606,7 @@ int bn_backward_t(const T* dy, const T* y, const unsigned char* mask, const T* x
                   const float* gamma, const float* save_mean, const float* save_invstd, T* dres, T* dx, float* dgamma,
                   float* dbeta, void* ws, size_t ws_bytes, hipStream_t st) {
     Geometry g;
-    const int th = part_threads();
+    const int th = kDefaultPartThreads;
     if (make_geometry(M, C, sizeof(T), g, th) != DAUC_OK) return DAUC_EINVAL;
     if (ws == nullptr || ws_bytes < ws_bytes_for(C) || !aligned16p(ws)) return DAUC_EINVAL;
     if (relu && y == nullptr && mask == nullptr) return DAUC_EINVAL;

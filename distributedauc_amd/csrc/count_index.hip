@@ -11,8 +11,6 @@
 // scatter passes into a cell-ordered table: counts_labeled_direct, counts_labeled_direct_slots; a
 // tuning build's dauc_set_index_form(1)) and its fault injection (dauc_set_direct_fault).
 
-#include <stdlib.h>
-
 #include "auc_eval_internal.h"
 
 namespace dauc {
@@ -615,14 +613,11 @@ int build_direct_index(const float* pos, const unsigned long long* Mp, int64_t M
     return launch_status();
 }
 
-int counts_labeled_direct_slots(const SlotSource& src, float* pos, int64_t Mcap, const float* scores,
-                                const void* labels, int label_dtype, int64_t begin, int64_t end,
-                                unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                                void* workspace, size_t workspace_bytes, hipStream_t st, unsigned* check) {
-    if (begin < 0 || end < begin || wins_ties == nullptr || pos == nullptr || src.slots == nullptr ||
-        src.parts < 1 || src.parts > kMaxSlotParts || (end > begin && (scores == nullptr || labels == nullptr)) ||
-        workspace == nullptr || Mcap < 1 || workspace_bytes < dauc_sort_workspace_size(Mcap) ||
-        !label_dtype_ok(label_dtype))
+int counts_labeled_direct_slots(const SlotSource& src, float* pos, int64_t Mcap, const LabeledQueries& q,
+                                unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
+                                unsigned* check) {
+    if (!q.valid() || pos == nullptr || src.slots == nullptr || src.parts < 1 || src.parts > kMaxSlotParts ||
+        workspace == nullptr || Mcap < 1 || workspace_bytes < dauc_sort_workspace_size(Mcap))
         return DAUC_EINVAL;
     const SortWorkspace ws = sort_workspace(workspace, Mcap);
     const SortWs& w = ws.sort;
@@ -639,9 +634,8 @@ int counts_labeled_direct_slots(const SlotSource& src, float* pos, int64_t Mcap,
                        dim3(kDirectThreads), 0, st, pos, src.m_eff, nw.blk, grp, nw.meta, nw.cstart, w.keys_b, table,
                        kCiCntWords);
     int rc = launch_status();
-    if (rc || end == begin) return rc;
-    return launch_ci(scores, labels, label_dtype, begin, end, nw, table, 0, wins_ties, nonfinite, st,
-                     CiForm::direct(verdict, grp, src.m_eff, check));
+    if (rc || q.empty()) return rc;
+    return launch_ci(q, nw, table, 0, st, CiForm::direct(verdict, grp, src.m_eff, check));
 }
 
 int64_t slotted_cells(int64_t Mcap) {
@@ -660,42 +654,29 @@ int64_t slotted_cnt_words() { return (int64_t(kCiMaxBlocks) * kCiBlock) / 4; }
 
 unsigned* slotted_meta_ptr(void* workspace, int64_t Mcap) { return sort_workspace(workspace, Mcap).count.meta; }
 
-int counts_labeled_slotted(const SlotSource& src, unsigned* stab, int64_t Mcap, const float* scores, const void* labels,
-                           int label_dtype, int64_t begin, int64_t end, unsigned long long* wins_ties,
-                           unsigned long long* nonfinite, unsigned* verdict, void* workspace, size_t workspace_bytes,
-                           hipStream_t st, unsigned* check) {
-    if (begin < 0 || end < begin || wins_ties == nullptr || stab == nullptr || src.slots == nullptr ||
-        src.parts < 1 || src.parts > kMaxSlotParts || (end > begin && (scores == nullptr || labels == nullptr)) ||
-        workspace == nullptr || Mcap < 1 || workspace_bytes < dauc_sort_workspace_size(Mcap) || check == nullptr ||
-        !label_dtype_ok(label_dtype))
+int counts_labeled_slotted(const SlotSource& src, unsigned* stab, int64_t Mcap, const LabeledQueries& q,
+                           unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
+                           unsigned* check) {
+    if (!q.valid() || stab == nullptr || src.slots == nullptr || src.parts < 1 || src.parts > kMaxSlotParts ||
+        workspace == nullptr || Mcap < 1 || workspace_bytes < dauc_sort_workspace_size(Mcap) || check == nullptr)
         return DAUC_EINVAL;
     const CountWs nw = sort_workspace(workspace, Mcap).count;
-    const int64_t gk0 = (Mcap + kSlotCountThreads - 1) / kSlotCountThreads;
+    const int64_t gk = (Mcap + kSlotCountThreads - 1) / kSlotCountThreads;
     const unsigned cells = static_cast<unsigned>(slotted_cells(Mcap));
-#ifdef DAUC_TUNING
-    // tuning builds: DAUC_SLOT_COUNT_WGS = this many count workgroups instead (each loops over keys)
-    int64_t gk = gk0;
-    if (const char* e = getenv("DAUC_SLOT_COUNT_WGS"); e && atoi(e) > 0 && atoi(e) <= 4096) gk = atoi(e);
-#else
-    const int64_t gk = gk0;
-#endif
     hipLaunchKernelGGL(direct_count_slots_kernel<true>, dim3(static_cast<unsigned>(gk)), dim3(kSlotCountThreads), 0,
                        st, src, Mcap, nw.l1, nw.meta, nw.cstart, nw.first, nullptr, stab, cells);  // (SLOT: see above)
     int rc = launch_status();
-    if (rc || end == begin) return rc;
-    return launch_ci(scores, labels, label_dtype, begin, end, nw, stab, 0, wins_ties, nonfinite, st,
+    if (rc || q.empty()) return rc;
+    return launch_ci(q, nw, stab, 0, st,
                      CiForm::slotted_two_step(verdict, src.m_eff, check, reinterpret_cast<const uint2*>(nw.cstart),
                                               cells, reinterpret_cast<unsigned long long*>(nw.first)));
 }
 
 int counts_labeled_direct_slotted(const float* pos, const unsigned long long* Mp, int64_t Mcap, unsigned* stab,
-                                  const float* scores, const void* labels, int label_dtype, int64_t begin,
-                                  int64_t end, unsigned long long* wins_ties, unsigned long long* nonfinite,
-                                  unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
-                                  const unsigned* ready_hist) {
-    if (begin < 0 || end < begin || wins_ties == nullptr || pos == nullptr || Mp == nullptr || stab == nullptr ||
-        ready_hist == nullptr || Mcap < 1 || workspace == nullptr || workspace_bytes < dauc_sort_workspace_size(Mcap) ||
-        (end > begin && (scores == nullptr || labels == nullptr)) || !label_dtype_ok(label_dtype))
+                                  const LabeledQueries& q, unsigned* verdict, void* workspace, size_t workspace_bytes,
+                                  hipStream_t st, const unsigned* ready_hist) {
+    if (!q.valid() || pos == nullptr || Mp == nullptr || stab == nullptr || ready_hist == nullptr || Mcap < 1 ||
+        workspace == nullptr || workspace_bytes < dauc_sort_workspace_size(Mcap))
         return DAUC_EINVAL;
     const CountWs nw = sort_workspace(workspace, Mcap).count;
     const unsigned cells = static_cast<unsigned>(slotted_cells(Mcap));
@@ -704,24 +685,20 @@ int counts_labeled_direct_slotted(const float* pos, const unsigned long long* Mp
                        dim3(kDirectThreads), 0, st, pos, Mcap, ready_hist, nw.l1, nw.meta, nw.cstart, nullptr, stab,
                        cells, Mp);
     int rc = launch_status();
-    if (rc || end == begin) return rc;
-    return launch_ci(scores, labels, label_dtype, begin, end, nw, stab, 0, wins_ties, nonfinite, st,
+    if (rc || q.empty()) return rc;
+    return launch_ci(q, nw, stab, 0, st,
                      CiForm::slotted_one_call(verdict, Mp, reinterpret_cast<const uint2*>(nw.cstart), cells));
 }
 
-int counts_labeled_direct(const float* pos, const unsigned long long* Mp, int64_t Mcap, const float* scores,
-                          const void* labels, int label_dtype, int64_t begin, int64_t end,
-                          unsigned long long* wins_ties, unsigned long long* nonfinite, unsigned* verdict,
-                          void* workspace, size_t workspace_bytes, hipStream_t st, const unsigned* ready_hist,
-                          unsigned* check) {
-    if (begin < 0 || end < begin || wins_ties == nullptr || (end > begin && (scores == nullptr || labels == nullptr)) ||
-        !label_dtype_ok(label_dtype))
-        return DAUC_EINVAL;
+int counts_labeled_direct(const float* pos, const unsigned long long* Mp, int64_t Mcap, const LabeledQueries& q,
+                          unsigned* verdict, void* workspace, size_t workspace_bytes, hipStream_t st,
+                          const unsigned* ready_hist, unsigned* check) {
+    if (!q.valid()) return DAUC_EINVAL;
     DirectIndex ix{};
     int rc = build_direct_index(pos, Mp, Mcap, workspace, workspace_bytes, st, &ix, ready_hist);
-    if (rc || end == begin) return rc;
-    return launch_ci(scores, labels, label_dtype, begin, end, sort_workspace(workspace, Mcap).count, ix.table, 0,
-                     wins_ties, nonfinite, st, CiForm::direct(verdict, ix.grp, Mp, check));
+    if (rc || q.empty()) return rc;
+    return launch_ci(q, sort_workspace(workspace, Mcap).count, ix.table, 0, st,
+                     CiForm::direct(verdict, ix.grp, Mp, check));
 }
 
 }  // namespace dauc

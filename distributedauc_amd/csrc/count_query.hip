@@ -6,8 +6,6 @@
 // counts_labeled_* (dauc_auc_eval_*) and from the sorted path (auc_sort.hip,
 // dauc_auc_counts_sorted_labeled; the index and its cost are described there and in count_index.h).
 
-#include <stdlib.h>
-
 #include "auc_query.h"
 #include "auc_eval_internal.h"
 
@@ -113,18 +111,12 @@ __device__ __forceinline__ void slot_tertiary(unsigned x, unsigned c, unsigned c
 // back in place); `sorted` is the slotted table of `slot_cells` cells. A cell's keys are its primary
 // window (+inf past its count), its secondary window past 4 keys and, past 8 (rare), its tertiary
 // run: W += M - (rank_lo + #keys <= x), T += #(== x); no straddling windows.
-#ifdef DAUC_TUNING
-// tuning builds: DAUC_QUERY_ABL (timing ablations of the SLOT query pass; WRONG counts): 1 = no
-// query loop (the prologue and the reduction only), 2 = the block words zeroed instead of loaded
-// and converted (every cell empty: the loop's windows all read the +inf pad window), 3 = no
-// end-of-kernel atomics, 4 = 1 + 3 (the prologue only)
-__device__ int g_query_abl = 0;
-#endif
 // SEC (SLOT only; round 6): ONE secondary window per lane per group of 4 queries instead of one per
 // query: cells of 5+ keys are ~0.6 % of the queries, so a lane loads the secondary window of its
 // group's first such query (the +inf pad when there is none) with the group's primaries, and counts
 // it with them; a second such query in the same group (~2e-4 of lane-groups) is counted at once.
 // 12 fewer live VGPRs per group and ~69 fewer VALU per group.
+// (SEC is only instantiated true; the per-query form went with its tuning knob.)
 template <typename LT, bool CHECK = false, bool SLOT = false, bool SEC = true>
 __global__ __launch_bounds__(kQueryThreads) void query_ci_kernel(const float* __restrict__ s,
                                                                 const LT* __restrict__ lab, int64_t begin,
@@ -215,23 +207,19 @@ __global__ __launch_bounds__(kQueryThreads) void query_ci_kernel(const float* __
         // the index into LDS with every load of a thread in flight before its first LDS store (a
         // load-store loop waits out one L2 round trip per iteration: 18 of them per thread)
         uint2 a[kL1Per], v[kBlkPer];
-#ifdef DAUC_TUNING
-        const bool abl2 = SLOT && g_query_abl == 2;
-#else
-        constexpr bool abl2 = false;
-#endif
         if constexpr (SLOT) {  // (loaded above)
 #pragma unroll
             for (int j = 0; j < kL1Per; ++j) a[j] = pre_a[j];
 #pragma unroll
-            for (int j = 0; j < kBlkPer; ++j) v[j] = abl2 ? uint2{0u, 0u} : pre_v[j];
+            for (int j = 0; j < kBlkPer; ++j)
+                v[j] = uint2(pre_v[j]);  // (through a temporary: a plain assignment schedules differently)
         } else {
 #pragma unroll
             for (int j = 0; j < kL1Per; ++j) a[j] = l1g[j * kQueryThreads + threadIdx.x];
 #pragma unroll
             for (int j = 0; j < kBlkPer; ++j) {
                 const int i = j * kQueryThreads + threadIdx.x;
-                v[j] = i < nb && !abl2 ? blkg[i] : uint2{0u, 0u};
+                v[j] = i < nb ? blkg[i] : uint2{0u, 0u};
             }
         }
         if (grp != nullptr) {
@@ -283,9 +271,6 @@ __global__ __launch_bounds__(kQueryThreads) void query_ci_kernel(const float* __
     const unsigned M32 = static_cast<unsigned>(M);
     unsigned long long w = 0, t = 0;
     unsigned nf = 0;  // CHECK: + #queries << 16
-#ifdef DAUC_TUNING
-    if (SLOT && (g_query_abl == 1 || g_query_abl == 4)) end = begin;  // no queries: the prologue (+ reduction)
-#endif
     const int64_t a0 = (begin + 3) & ~int64_t(3);
     const int64_t head = a0 < end ? a0 : end;
     const int64_t stride = int64_t(gridDim.x) * kQueryThreads;
@@ -599,9 +584,6 @@ __global__ __launch_bounds__(kQueryThreads) void query_ci_kernel(const float* __
         if constexpr (CHECK) red[CHECK ? 3 : 0][wid] = ckw;
     }
     __syncthreads();
-#ifdef DAUC_TUNING
-    if (SLOT && g_query_abl >= 3) return;  // no end-of-kernel atomics
-#endif
     if (threadIdx.x == 0) {
         unsigned long long bw = 0, bt = 0, bn = 0, bc = 0;
         for (int i = 0; i < kQueryThreads / kWave; ++i) {
@@ -618,7 +600,7 @@ __global__ __launch_bounds__(kQueryThreads) void query_ci_kernel(const float* __
         } else {
             // round 6 (the two-step's query pass): its workgroups finish together, and 3-4 atomics
             // each on the record's one line serialise (~8 us at 256 workgroups and 2^21 queries,
-            // DAUC_QUERY_ABL 3; the one-call pass, 8x the queries per workgroup, measured 1 us
+            // measured by an ablation since removed; the one-call pass, 8x the queries per workgroup, measured 1 us
             // slower with the groups and keeps the plain atomics). Group g = blockIdx % 8 adds into
             // its own line of red8 (256 B apart; zeroed by the count pass before this launch), takes
             // the group's ticket after its adds are acknowledged, and the group's last arriver adds
@@ -649,54 +631,37 @@ __global__ __launch_bounds__(kQueryThreads) void query_ci_kernel(const float* __
 }
 
 // the one place an instantiation is chosen: CHECK by the check word, SLOT by the slotted table's
-// byte counts, SEC always (a tuning build's DAUC_QUERY_SEC=0 runs the per-query secondary window)
+// byte counts; SEC is only instantiated true (the carried secondary window)
 template <typename LT>
-auto pick_query(bool check, bool slot, bool sec) -> decltype(&query_ci_kernel<LT>) {
-    if (slot && sec) return check ? &query_ci_kernel<LT, true, true, true> : &query_ci_kernel<LT, false, true, true>;
-#ifdef DAUC_TUNING
-    if (slot) return check ? &query_ci_kernel<LT, true, true, false> : &query_ci_kernel<LT, false, true, false>;
-#endif
+auto pick_query(bool check, bool slot) -> decltype(&query_ci_kernel<LT>) {
+    if (slot) return check ? &query_ci_kernel<LT, true, true, true> : &query_ci_kernel<LT, false, true, true>;
     return check ? &query_ci_kernel<LT, true> : &query_ci_kernel<LT>;
 }
 
+// `lab` is q.labels with its element type
 template <typename LT>
-int launch_ci_typed(const float* s, const LT* lab, int64_t begin, int64_t end, const CountWs& cw, const unsigned* table,
-                    int64_t M, unsigned long long* out, unsigned long long* nonfinite, hipStream_t st, const CiForm& f) {
-    const dim3 grid(query_grid(end - begin)), block(kQueryThreads);
+int launch_ci_typed(const LabeledQueries& q, const LT* lab, const CountWs& cw, const unsigned* table, int64_t M,
+                    hipStream_t st, const CiForm& f) {
+    const dim3 grid(query_grid(q.end - q.begin)), block(kQueryThreads);
     const size_t lds = (size_t(kCiTop) + kCiMaxBlocks) * 8 + (f.grp ? size_t(kDirectMaxGroups) * 4 : 0);
-    bool sec = true;  // the carried secondary window (query_ci_kernel's SEC)
-#ifdef DAUC_TUNING
-    {
-        static int abl = -1;
-        if (abl < 0) {
-            const char* e = getenv("DAUC_QUERY_ABL");
-            abl = e ? atoi(e) : 0;
-            if (hipMemcpyToSymbol(HIP_SYMBOL(g_query_abl), &abl, sizeof(int)) != hipSuccess) return DAUC_EINVAL;
-        }
-        const char* e = getenv("DAUC_QUERY_SEC");  // 0: a secondary window per query (the round-6 form)
-        sec = !(e && atoi(e) == 0);
-    }
-#endif
     // dynamic + the kernel's static reduction rows must fit the CU's 160 KB of LDS (a launch past it
     // aborts the queue: HSA_STATUS_ERROR_INVALID_ALLOCATION)
     static_assert((size_t(kCiTop) + kCiMaxBlocks) * 8 + size_t(kDirectMaxGroups) * 4 +
                           4 * (kQueryThreads / kWave) * 8 <= 160 * 1024,
                   "the count-index query's LDS");
     const bool slot = f.slot_counts != nullptr;
-    hipLaunchKernelGGL(pick_query<LT>(f.check != nullptr, slot, sec), grid, block, lds, st, s, lab, begin, end, cw.meta,
-                       cw.l1, slot ? f.slot_counts : cw.blk, table, M, out, nonfinite, f.verdict, f.grp, f.Mp, f.check,
-                       f.slot_cells, f.red8);
+    hipLaunchKernelGGL(pick_query<LT>(f.check != nullptr, slot), grid, block, lds, st, q.scores, lab, q.begin, q.end,
+                       cw.meta, cw.l1, slot ? f.slot_counts : cw.blk, table, M, q.wins_ties, q.nonfinite, f.verdict,
+                       f.grp, f.Mp, f.check, f.slot_cells, f.red8);
     return launch_status();
 }
 
 }  // namespace
 
-int launch_ci(const float* scores, const void* labels, int label_dtype, int64_t begin, int64_t end, const CountWs& cw,
-              const unsigned* table, int64_t M, unsigned long long* out, unsigned long long* nonfinite, hipStream_t st,
+int launch_ci(const LabeledQueries& q, const CountWs& cw, const unsigned* table, int64_t M, hipStream_t st,
               const CiForm& form) {
-    return with_labels(labels, label_dtype, [&](auto* lab) {
-        return launch_ci_typed(scores, lab, begin, end, cw, table, M, out, nonfinite, st, form);
-    });
+    return with_labels(q.labels, q.label_dtype,
+                       [&](auto* lab) { return launch_ci_typed(q, lab, cw, table, M, st, form); });
 }
 
 }  // namespace dauc

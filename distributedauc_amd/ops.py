@@ -161,7 +161,8 @@ def surrogate_fwdbwd(h: torch.Tensor, y: torch.Tensor, abalpha: torch.Tensor, p_
             raise ValueError("grad3 needs 3 contiguous fp32 slots")
     if loss is not None:
         _require(loss, "loss", torch.float32, dev)
-    # variants run in the tuning build, whose workspace also holds the stamp region
+    # variants run in the tuning build: one workspace size and layout in both builds (surrogate.hip,
+    # dauc_surrogate_workspace_size), the variants' scratch kept apart from the product's all the same
     L = _lib.load() if variant == 0 else _lib.tuning()
     nbytes = L.dauc_surrogate_workspace_size(B)
     ws = workspaces.get(dev, "surrogate" if variant == 0 else "surrogate_tuning", nbytes)
@@ -396,7 +397,8 @@ def _eval_args(scores: torch.Tensor, labels: torch.Tensor):
     if n == 0:
         raise ValueError("empty score vector")
     L = _lib.load()
-    # keyed by library too: the tuning build's evaluation workspace also holds its range-slot path
+    # keyed by library too, so each build is asked for its own size; today both lay the evaluation
+    # workspace out alike (auc_eval.hip, eval_ws)
     nbytes = _eval_ws_bytes.get((id(L), n))
     if nbytes is None:
         nbytes = _eval_ws_bytes[(id(L), n)] = L.dauc_auc_eval_workspace_size(n)

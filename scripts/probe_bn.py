@@ -1,7 +1,6 @@
 """Times the fused BN forward (stats + apply, ReLU mask) and backward (reduce + dx, from the mask;
 with and without the residual gradient) at the ResNet-50 b256 layer shapes through the C ABI, one
-JSON line per shape. The row-block walk follows DAUC_BN_INTERLEAVE / DAUC_BN_ROWBLOCKS (read once
-per process), so A/B runs are separate processes.
+JSON line per shape.
 
   python scripts/probe_bn.py [--reps 30] [--tag name]
 """
@@ -54,8 +53,7 @@ def main() -> None:
                                          _ptr(invstd), _ptr(dres) if res else None, _ptr(dx), _ptr(dgamma),
                                          _ptr(dbeta), _ptr(ws), ws.numel(), st), "backward")
 
-        out = {"tag": a.tag, "shape": [N, C, H, W], "M": M,
-               "interleave": os.environ.get("DAUC_BN_INTERLEAVE", "0")}
+        out = {"tag": a.tag, "shape": [N, C, H, W], "M": M}
         for name, fn in (("fwd", fwd), ("bwd", lambda: bwd(False)), ("bwd_res", lambda: bwd(True))):
             for _ in range(3):
                 fn()

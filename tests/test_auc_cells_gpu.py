@@ -305,3 +305,33 @@ def test_index_forms_agree_one_call(dev, ops, case):
     assert recs[0] == recs[1], (case, recs)
     want = 2 if case in ("cell_15", "p_over_half") else 1
     assert recs[0][7] == want, (case, recs[0])
+
+
+SHAPE_NMAX = 1 << 25
+
+
+@pytest.fixture(scope="module")
+def shape_data():
+    """U(0,1) fp32 scores and int8 labels with 0.1 % positives, 2^25 of each (33.7 k positives: well
+    inside the count index's 219,838); every shape case below is a prefix."""
+    rng = np.random.default_rng(11)
+    return rng.random(SHAPE_NMAX, dtype=np.float32), _labels(rng, SHAPE_NMAX, 0.001)
+
+
+@pytest.mark.parametrize("n,label_offset", [((1 << 23) - 1, 0), (1 << 23, 0), ((1 << 25) - 1, 0), (1 << 25, 0),
+                                            ((1 << 23) + 1, 1)])
+def test_compaction_shapes_one_call(dev, shape_data, n, label_offset):
+    """The product library's one-call evaluation at the sizes where the unordered compaction changes
+    shape (auc_count.hip, compact_unordered): 256 threads x 8 label groups below 2^23 labels, 512 x 8
+    from 2^23, 256 x 32 from 2^25 -- the smallest inputs that reach the 512-thread and the wide shape,
+    so a launcher that pairs a shape with the wrong block size shows here. The last case hands over
+    the labels as a [1:] view of a larger array: not 16-byte aligned, so the 512-thread shape runs its
+    per-group bounds-checked label loads. (W, T, P, N) exact against the C oracle."""
+    from distributedauc_amd import ops
+
+    s, y = shape_data[0][:n], shape_data[1][:n]
+    e = coracle.auc_counts(y.astype(np.int64), s)
+    ty = T(np.concatenate([np.zeros(label_offset, np.int8), y]), dev)[label_offset:]
+    assert ty.data_ptr() % 16 == label_offset
+    W, Tt, P, N, bad, other = ops.auc_eval_counts(T(s, dev), ty)
+    assert (W, Tt, P, N) == (e["wins"], e["ties"], e["P"], e["N"]), (n, label_offset)

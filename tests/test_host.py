@@ -104,3 +104,14 @@ def test_run_label_format():
     p = parameters.parse("--split_index 499 --neg_keep_ratio 0.4 --I 64".split())
     s = run_label(p, 16)
     assert s.startswith("_size_16_lr_0.1_T0_5000_gamma_2000_p_0.71_I_64_local_batchsize_32")
+
+
+def test_kernel_sources_read_no_environment():
+    """The launchers' geometry is fixed in the sources: no file under distributedauc_amd/csrc reads an
+    environment variable (a stray variable in a shell must not change a grid)."""
+    from pathlib import Path
+
+    csrc = Path(backbone.__file__).resolve().parent / "csrc"
+    files = sorted(p for p in csrc.iterdir() if p.is_file())
+    assert len(files) > 10, files
+    assert [p.name for p in files if "getenv" in p.read_text(errors="replace")] == []
