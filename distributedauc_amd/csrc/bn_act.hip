@@ -30,6 +30,9 @@
 #include <type_traits>
 
 #include "dauc_internal.h"
+#ifdef DAUC_TUNING
+#include "dauc_tuning.h"
+#endif
 
 namespace dauc {
 namespace {
@@ -48,7 +51,11 @@ constexpr int kFinSubsets = kFinThreads / 16;
 constexpr int kRowBlockTarget = 256;
 static_assert(kRowBlockTarget >= 1 && kRowBlockTarget <= kMaxRowBlocks, "partial rows fit the workspace");
 constexpr int kUnroll = 8;          // row passes whose loads are in flight together
+constexpr int kFwdUnroll = kUnroll;      // passes per group of the statistics pass (one load per pass)
+constexpr int kBwdUnroll = kUnroll / 2;  // of the backward reduce (two or three loads per pass)
+constexpr int kFinUnroll = 4;       // finalize: row subsets' loads in flight per thread before any fold
 constexpr int kApplyVecs = 4;       // 16-byte vectors per thread in the elementwise kernels
+constexpr int64_t kApplyBlockVecs = int64_t(kApplyVecs) * kBnThreads;  // per elementwise workgroup
 
 template <typename T>
 struct VecT;
@@ -233,7 +240,7 @@ __global__ __launch_bounds__(TH) void bn_partial_kernel(
         }
     };
     // full groups of U passes: every load of the group is issued before any math
-    constexpr int U = STATS ? kUnroll : kUnroll / 2;
+    constexpr int U = STATS ? kFwdUnroll : kBwdUnroll;
     int64_t r = rs + r0;
     const int64_t step = int64_t(RPB) * U;
     for (; r + step - RPB < re; r += step) {
@@ -312,7 +319,7 @@ __device__ __forceinline__ void sum_partials(const float* __restrict__ partials,
                                              int C, int cbase, double (*red)[kFinSubsets][64], double& t1,
                                              double& t2) {
     constexpr int NP = STATS ? 3 : 2;
-    constexpr int FU = 4;  // row subsets' loads in flight per thread before any fold
+    constexpr int FU = kFinUnroll;
     const int cq = threadIdx.x % 16, j = threadIdx.x / 16;
     const int c = cbase + cq * 4;
     double a1[4] = {0, 0, 0, 0}, a2[4] = {0, 0, 0, 0};
@@ -539,6 +546,10 @@ BnWs carve(void* ws, int C) {
 
 bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// elementwise grid: workgroups over nvec vectors; HOIST when a thread's channels never change
+int64_t apply_blocks(int64_t nvec) { return (nvec + kApplyBlockVecs - 1) / kApplyBlockVecs; }
+bool apply_hoists(int CV) { return kBnThreads % CV == 0; }
+
 template <typename T, bool BWD, int GMODE, bool RELU, bool RES, bool MASK = false>
 int launch_elementwise(const T* x, const T* g_in, const T* aux, T* out, int64_t M, int C, const float* p0,
                        const float* p1, const float* p2, const float* p3, hipStream_t st,
@@ -546,10 +557,9 @@ int launch_elementwise(const T* x, const T* g_in, const T* aux, T* out, int64_t 
     constexpr int N = VecT<T>::N;
     const int CV = C / N;
     const int64_t nvec = M * CV;
-    const int64_t per_block = int64_t(kApplyVecs) * kBnThreads;
-    const int64_t grid = (nvec + per_block - 1) / per_block;
+    const int64_t grid = apply_blocks(nvec);
     if (grid > 0x7fffffffLL) return DAUC_EINVAL;
-    if (kBnThreads % CV == 0)
+    if (apply_hoists(CV))
         hipLaunchKernelGGL((bn_elementwise_kernel<T, BWD, GMODE, RELU, RES, true, MASK>), dim3(unsigned(grid)),
                            dim3(kBnThreads), 0, st, x, g_in, aux, out, nvec, CV, p0, p1, p2, p3, mask);
     else
@@ -688,5 +698,30 @@ int dauc_bn_act_backward(const void* dy, const void* y, const uint8_t* relu_mask
                              workspace_bytes, st);
     return DAUC_EINVAL;
 }
+
+#ifdef DAUC_TUNING
+// tuning builds: the launch plan of a BN layer (include/dauc_tuning.h), from the launchers' own
+// geometry and constants; host arithmetic only
+int dauc_bn_launch_plan(int64_t M, int C, int dtype, int64_t out[DAUC_BN_PLAN_WORDS]) {
+    if (out == nullptr || (dtype != DAUC_DTYPE_BF16 && dtype != DAUC_DTYPE_F32)) return DAUC_EINVAL;
+    Geometry g;
+    const int rc = make_geometry(M, C, dtype == DAUC_DTYPE_BF16 ? 2 : 4, g, kDefaultPartThreads);
+    if (rc != DAUC_OK) return rc;
+    const int CV = C / g.N;
+    out[0] = g.TPR;
+    out[1] = g.RPB;
+    out[2] = g.ctiles;
+    out[3] = g.nrb;
+    out[4] = g.rows;
+    out[5] = int64_t(g.RPB) * kFwdUnroll;
+    out[6] = int64_t(g.RPB) * kBwdUnroll;
+    out[7] = int64_t(kFinSubsets) * kFinUnroll;
+    out[8] = kFinSubsets;
+    out[9] = kApplyBlockVecs;
+    out[10] = apply_blocks(M * CV);
+    out[11] = apply_hoists(CV) ? 1 : 0;
+    return DAUC_OK;
+}
+#endif
 
 }  // extern "C"

@@ -96,6 +96,21 @@ int dauc_probe_tr16(short* out, dauc_stream_t stream);
  * 64 / 128-pixel chunks, where they fit (tests, A/B runs). Process-global; tuning builds only. */
 int dauc_set_wgrad_form(int form);
 
+/* The launch plan of dauc_bn_act_forward / _backward for an [M, C] activation (csrc/bn_act.hip), from
+ * the geometry and constants the launchers use; host arithmetic only, no GPU is touched. For the
+ * tests: they derive from it which loops of the kernels a shape runs, so that a retune cannot leave
+ * the main loops untested. out[0..11]:
+ *   0 TPR, threads per row            1 RPB, rows per pass             2 ctiles, channel tiles
+ *   3 nrb, row blocks per tile        4 rows per row block             5 rows per forward group
+ *   6 rows per backward group         7 finalize: partial rows per group (subsets x unroll)
+ *   8 finalize: row subsets           9 elementwise: vectors per workgroup
+ *  10 elementwise: workgroups        11 elementwise: 1 if a thread's channels are hoisted
+ * A pass is RPB rows; a group is the passes whose loads the partial-sum kernel issues together (its
+ * main loop runs once per whole group of a block's passes, the tail once per remaining pass); the
+ * finalize's grouped loop runs when nrb > out[7] - out[8]. DAUC_EINVAL for shapes the kernels refuse. */
+#define DAUC_BN_PLAN_WORDS 12
+int dauc_bn_launch_plan(int64_t M, int C, int dtype, int64_t out[DAUC_BN_PLAN_WORDS]);
+
 #ifdef __cplusplus
 }
 #endif
