@@ -109,8 +109,10 @@ TUNING_SIGNATURES = {
     "dauc_probe_tr16": (_int, [_vp, _vp]),
     "dauc_set_wgrad_form": (_int, [_int]),
     "dauc_bn_launch_plan": (_int, [_i64, _int, _int, ctypes.POINTER(_i64)]),
+    "dauc_conv3x3_wgrad_launch_plan": (_int, [_i64, _int, _int, _int, _int, _int, _int, _int, ctypes.POINTER(_i64)]),
 }
 BN_PLAN_WORDS = 12  # DAUC_BN_PLAN_WORDS
+WGRAD_PLAN_WORDS = 18  # DAUC_WGRAD_PLAN_WORDS
 TUNING_LIB_PATH = Path(os.environ.get("DAUC_TUNING_LIB", PKG_DIR.parent / "tuning" / "libdauc_tuning.so"))
 
 _lib = None

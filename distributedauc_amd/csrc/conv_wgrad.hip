@@ -28,6 +28,9 @@
 #include <hip/hip_bf16.h>
 
 #include "dauc_internal.h"
+#ifdef DAUC_TUNING
+#include "dauc_tuning.h"
+#endif
 
 namespace dauc {
 namespace {
@@ -212,11 +215,14 @@ constexpr int kARow = 80;
 // with its own L2; the tiles of one split read the same dy rows (same output-channel tile) or the
 // same input window (same input-channel tile), so when the split count allows, a split's tiles are
 // placed on one XCD (XCD x runs splits x, x + 8, ...) and share those reads in its L2.
+// whether the window kernel's grid is placed that way (the kernel and the host's launch plan)
+__host__ __device__ __forceinline__ bool xcd_placed(int tiles, int splits) { return tiles > 1 && splits % 8 == 0; }
+
 __device__ __forceinline__ void tile_split(int& tile, int& split) {
     const int tiles = static_cast<int>(gridDim.x), splits = static_cast<int>(gridDim.y);
     tile = static_cast<int>(blockIdx.x);
     split = static_cast<int>(blockIdx.y);
-    if (tiles > 1 && splits % 8 == 0) {
+    if (xcd_placed(tiles, splits)) {
         const int b = tile + tiles * split, k = b / 8;
         tile = k % tiles;
         split = (k / tiles) * 8 + b % 8;
@@ -591,6 +597,71 @@ int64_t split_count(int64_t tiles, int64_t chunks) {
     int64_t S = (256 + tiles - 1) / tiles;
     return S > chunks ? chunks : S;
 }
+
+// the (NV, KS) instantiations dauc_conv3x3_wgrad's switch holds
+bool win_case_known(int nv, int ks) { return nv >= 1 && nv <= kMaxWinVec && (ks == 2 || ks == 4); }
+
+// Everything dauc_conv3x3_wgrad decides on the host before it launches: the form and its geometry
+// (cps set), the grid, the window kernel's instantiation and LDS. The launcher launches from this;
+// the tuning build's dauc_conv3x3_wgrad_launch_plan reports it.
+struct WgradPlan {
+    bool window;
+    WinGeom wg;    // window form
+    WgradGeom gg;  // gather form
+    int64_t tiles, chunks, cps, splits;
+    bool xcd;    // tile_split permutes (window form only)
+    int nv, ks;  // wgrad3x3_win_kernel<nv, ks>
+    size_t lds;  // dynamic (window) or static (gather) LDS bytes of a workgroup
+    size_t workspace;  // bytes the launch needs (0: one split, written to dw)
+};
+
+// DAUC_EINVAL for every shape the launcher refuses
+int wgrad_plan(int64_t N, int H, int W, int Ci, int Ho, int Wo, int Co, int stride, WgradPlan& p) {
+    if (N < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || Ci < kBC || Co < kBM || Ci % kBC || Co % kBM) return DAUC_EINVAL;
+    if (stride != 1 && stride != 2) return DAUC_EINVAL;
+    if (Ho != (H + 2 - 3) / stride + 1 || Wo != (W + 2 - 3) / stride + 1) return DAUC_EINVAL;  // pad 1
+    if (N * int64_t(H) * W > (int64_t(1) << 31) || N * int64_t(Ho) * Wo > (int64_t(1) << 31)) return DAUC_EINVAL;
+    p.tiles = int64_t(Co / kBM) * (Ci / kBC);
+    if (p.tiles > 0x7fffffffLL) return DAUC_EINVAL;
+    p.workspace = dauc_conv3x3_wgrad_workspace_size(N, Ho, Wo, Ci, Co);
+    const int64_t Smax = p.workspace ? int64_t(p.workspace / (size_t(Co) * kTaps * size_t(Ci) * sizeof(float))) : 1;
+    p.window = win_geom(N, H, W, Ci, Ho, Wo, Co, stride, p.wg);
+    if (p.window) {
+        p.chunks = p.wg.chunks;
+    } else {
+        WgradGeom& g = p.gg;
+        g.N = static_cast<int>(N);
+        g.H = H;
+        g.W = W;
+        g.Ci = Ci;
+        g.Ho = Ho;
+        g.Wo = Wo;
+        g.Co = Co;
+        g.stride = stride;
+        g.P = N * Ho * Wo;
+        g.chunks = (g.P + kKT - 1) / kKT;
+        g.ctiles = Ci / kBC;
+        p.chunks = g.chunks;
+    }
+    const int64_t S = split_count(p.tiles, p.chunks) < Smax ? split_count(p.tiles, p.chunks) : Smax;
+    p.cps = (p.chunks + S - 1) / S;
+    p.splits = (p.chunks + p.cps - 1) / p.cps;  // every split owns at least one chunk
+    if (p.splits > 65535) return DAUC_EINVAL;
+    if (p.window) {
+        p.wg.cps = p.cps;
+        p.nv = p.wg.nvec;
+        p.ks = p.wg.KT / 32;
+        if (!win_case_known(p.nv, p.ks)) return DAUC_EINVAL;
+        p.xcd = xcd_placed(static_cast<int>(p.tiles), static_cast<int>(p.splits));
+        p.lds = win_lds_bytes(p.wg);
+    } else {
+        p.gg.cps = p.cps;
+        p.nv = p.ks = 0;
+        p.xcd = false;
+        p.lds = size_t(1 + kTaps) * kTile * sizeof(short);
+    }
+    return DAUC_OK;
+}
 }  // namespace
 
 size_t dauc_conv3x3_wgrad_workspace_size(int64_t N, int Ho, int Wo, int Ci, int Co) {
@@ -606,33 +677,23 @@ size_t dauc_conv3x3_wgrad_workspace_size(int64_t N, int Ho, int Wo, int Ci, int 
 int dauc_conv3x3_wgrad(const void* x, const void* dy, int dtype, int64_t N, int H, int W, int Ci, int Ho, int Wo,
                        int Co, int stride, float* dw, void* workspace, size_t workspace_bytes, dauc_stream_t stream) {
     if (x == nullptr || dy == nullptr || dw == nullptr || dtype != DAUC_DTYPE_BF16) return DAUC_EINVAL;
-    if (N < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || Ci < kBC || Co < kBM || Ci % kBC || Co % kBM) return DAUC_EINVAL;
-    if (stride != 1 && stride != 2) return DAUC_EINVAL;
-    if (Ho != (H + 2 - 3) / stride + 1 || Wo != (W + 2 - 3) / stride + 1) return DAUC_EINVAL;  // pad 1
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dw)) & 15u)
         return DAUC_EINVAL;
-    if (N * int64_t(H) * W > (int64_t(1) << 31) || N * int64_t(Ho) * Wo > (int64_t(1) << 31)) return DAUC_EINVAL;
-    const int64_t tiles = int64_t(Co / kBM) * (Ci / kBC);
-    const size_t need = dauc_conv3x3_wgrad_workspace_size(N, Ho, Wo, Ci, Co);
-    const int64_t Smax = need ? int64_t(need / (size_t(Co) * kTaps * size_t(Ci) * sizeof(float))) : 1;
-    if (need && (workspace == nullptr || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u)))
+    WgradPlan p;
+    if (wgrad_plan(N, H, W, Ci, Ho, Wo, Co, stride, p) != DAUC_OK) return DAUC_EINVAL;
+    if (p.workspace &&
+        (workspace == nullptr || workspace_bytes < p.workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u)))
         return DAUC_EINVAL;
-    if (tiles > 0x7fffffffLL) return DAUC_EINVAL;
     hipStream_t st = as_hip(stream);
-    WinGeom wg;
-    int64_t splits;
-    float* target;
-    if (win_geom(N, H, W, Ci, Ho, Wo, Co, stride, wg)) {
-        const int64_t S = split_count(tiles, wg.chunks) < Smax ? split_count(tiles, wg.chunks) : Smax;
-        wg.cps = (wg.chunks + S - 1) / S;
-        splits = (wg.chunks + wg.cps - 1) / wg.cps;  // every split owns at least one chunk
-        if (splits > 65535) return DAUC_EINVAL;
-        target = splits > 1 ? static_cast<float*>(workspace) : dw;
-        const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(splits));
-        const size_t lds = win_lds_bytes(wg);
-        const __hip_bfloat16* xb = static_cast<const __hip_bfloat16*>(x);
-        const __hip_bfloat16* db = static_cast<const __hip_bfloat16*>(dy);
-        switch (wg.nvec * 8 + wg.KT / 32) {
+    const int64_t splits = p.splits;
+    float* target = splits > 1 ? static_cast<float*>(workspace) : dw;
+    const dim3 grid(static_cast<unsigned>(p.tiles), static_cast<unsigned>(splits));
+    const __hip_bfloat16* xb = static_cast<const __hip_bfloat16*>(x);
+    const __hip_bfloat16* db = static_cast<const __hip_bfloat16*>(dy);
+    if (p.window) {
+        const WinGeom& wg = p.wg;
+        const size_t lds = p.lds;
+        switch (p.nv * 8 + p.ks) {
 #define DAUC_WIN_CASE(NV, KS) \
     case NV * 8 + KS:         \
         hipLaunchKernelGGL((wgrad3x3_win_kernel<NV, KS>), grid, dim3(kWgThreads), lds, st, xb, db, wg, target); break;
@@ -656,26 +717,7 @@ int dauc_conv3x3_wgrad(const void* x, const void* dy, int dtype, int64_t N, int 
             default: return DAUC_EINVAL;
         }
     } else {
-        WgradGeom g;
-        g.N = static_cast<int>(N);
-        g.H = H;
-        g.W = W;
-        g.Ci = Ci;
-        g.Ho = Ho;
-        g.Wo = Wo;
-        g.Co = Co;
-        g.stride = stride;
-        g.P = N * Ho * Wo;
-        g.chunks = (g.P + kKT - 1) / kKT;
-        g.ctiles = Ci / kBC;
-        const int64_t S = split_count(tiles, g.chunks) < Smax ? split_count(tiles, g.chunks) : Smax;
-        g.cps = (g.chunks + S - 1) / S;
-        splits = (g.chunks + g.cps - 1) / g.cps;
-        if (splits > 65535) return DAUC_EINVAL;
-        target = splits > 1 ? static_cast<float*>(workspace) : dw;
-        hipLaunchKernelGGL(wgrad3x3_kernel, dim3(static_cast<unsigned>(tiles), static_cast<unsigned>(splits)),
-                           dim3(kWgThreads), 0, st, static_cast<const __hip_bfloat16*>(x),
-                           static_cast<const __hip_bfloat16*>(dy), g, target);
+        hipLaunchKernelGGL(wgrad3x3_kernel, grid, dim3(kWgThreads), 0, st, xb, db, p.gg, target);
     }
     int rc = launch_status();
     if (rc != DAUC_OK || splits == 1) return rc;
@@ -686,6 +728,36 @@ int dauc_conv3x3_wgrad(const void* x, const void* dy, int dtype, int64_t N, int 
 int dauc_set_wgrad_form(int form) {
     if (form < 0 || form > 5) return DAUC_EINVAL;
     g_wgrad_form = form;
+    return DAUC_OK;
+}
+
+// tuning builds: the launch plan of dauc_conv3x3_wgrad (include/dauc_tuning.h), from the function
+// the launcher launches from; host arithmetic only
+int dauc_conv3x3_wgrad_launch_plan(int64_t N, int H, int W, int Ci, int Ho, int Wo, int Co, int stride,
+                                   int64_t out[DAUC_WGRAD_PLAN_WORDS]) {
+    if (out == nullptr) return DAUC_EINVAL;
+    WgradPlan p;
+    const int rc = wgrad_plan(N, H, W, Ci, Ho, Wo, Co, stride, p);
+    if (rc != DAUC_OK) return rc;
+    const WinGeom& wg = p.wg;
+    out[0] = p.window ? 1 : 0;
+    out[1] = p.window ? wg.KT : kKT;
+    out[2] = p.window ? wg.shared : 0;
+    out[3] = p.window ? wg.R : 0;
+    out[4] = p.window ? wg.KP : 0;
+    out[5] = p.window ? wg.Wd : 0;
+    out[6] = p.window ? wg.npos : 0;
+    out[7] = p.nv;
+    out[8] = p.window && wg.shared ? (wg.R >= wg.Ho ? wg.R / wg.Ho : 1) : 0;
+    out[9] = p.tiles;
+    out[10] = p.chunks;
+    out[11] = p.cps;
+    out[12] = p.splits;
+    out[13] = p.chunks - (p.splits - 1) * p.cps;
+    out[14] = p.window ? wg.GR - (p.chunks - 1) * wg.R : p.gg.P - (p.chunks - 1) * kKT;
+    out[15] = p.xcd ? 1 : 0;
+    out[16] = static_cast<int64_t>(p.lds);
+    out[17] = p.ks;
     return DAUC_OK;
 }
 

@@ -111,6 +111,24 @@ int dauc_set_wgrad_form(int form);
 #define DAUC_BN_PLAN_WORDS 12
 int dauc_bn_launch_plan(int64_t M, int C, int dtype, int64_t out[DAUC_BN_PLAN_WORDS]);
 
+/* The launch plan of dauc_conv3x3_wgrad (csrc/conv_wgrad.hip) for a shape, from the one function the
+ * launcher itself launches from, under the form dauc_set_wgrad_form chose; host arithmetic only, no
+ * GPU is touched. For the tests: they derive from it which loops of the two kernels a shape runs
+ * (a split's chunk loop reaches its steady state from 3 chunks on), so that a retune of the split
+ * count or the layouts cannot leave those loops untested. out[0..17]:
+ *   0 form: 0 gather, 1 window        1 KT, pixel rows of a chunk's dy tile (gather: 64)
+ *   2 shared window rows (0 / 1)      3 R, output rows per chunk       4 KP = R * Wo, its pixels
+ *   5 Wd = W + 2, window row width    6 npos, window positions         7 nvec, window vectors per thread
+ *   8 images per chunk (0: not shared)                                 9 tiles (grid x)
+ *  10 chunks                         11 cps, chunks per split         12 splits (grid y)
+ *  13 chunks of the last split       14 output rows (window) / pixels (gather) of the last chunk
+ *  15 1 if the grid is placed by XCD (tile_split permutes)            16 LDS bytes of a workgroup
+ *  17 KS = KT / 32, k-steps per chunk: the kernel is wgrad3x3_win_kernel<nvec, KS> (gather: 0)
+ * Words 2..8 and 17 are 0 in the gather form. DAUC_EINVAL for shapes the launcher refuses. */
+#define DAUC_WGRAD_PLAN_WORDS 18
+int dauc_conv3x3_wgrad_launch_plan(int64_t N, int H, int W, int Ci, int Ho, int Wo, int Co, int stride,
+                                   int64_t out[DAUC_WGRAD_PLAN_WORDS]);
+
 #ifdef __cplusplus
 }
 #endif
