@@ -110,9 +110,11 @@ TUNING_SIGNATURES = {
     "dauc_set_wgrad_form": (_int, [_int]),
     "dauc_bn_launch_plan": (_int, [_i64, _int, _int, ctypes.POINTER(_i64)]),
     "dauc_conv3x3_wgrad_launch_plan": (_int, [_i64, _int, _int, _int, _int, _int, _int, _int, ctypes.POINTER(_i64)]),
+    "dauc_sort_table_plan": (_int, [_i64, ctypes.POINTER(_i64)]),
 }
 BN_PLAN_WORDS = 12  # DAUC_BN_PLAN_WORDS
 WGRAD_PLAN_WORDS = 18  # DAUC_WGRAD_PLAN_WORDS
+SORT_PLAN_WORDS = 16  # DAUC_SORT_PLAN_WORDS
 TUNING_LIB_PATH = Path(os.environ.get("DAUC_TUNING_LIB", PKG_DIR.parent / "tuning" / "libdauc_tuning.so"))
 
 _lib = None

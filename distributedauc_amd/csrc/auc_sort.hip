@@ -29,6 +29,9 @@
 
 #include "auc_eval_internal.h"
 #include "auc_query.h"
+#ifdef DAUC_TUNING
+#include "dauc_tuning.h"
+#endif
 
 namespace dauc {
 namespace {
@@ -36,6 +39,8 @@ namespace {
 // the distinct-key index of tie-heavy tables (dk_*_kernel below)
 constexpr int kDkUse = 0, kDkD = 1;              // meta words; kCiOk, kCiCells, kCiBlocks: the plan's
 constexpr int kDkScanThreads = 1024;
+// tiles each thread of the one-workgroup dk_scan_kernel takes (2 or more past 1,048,576 table keys)
+__host__ __device__ inline int64_t dk_scan_run(int64_t ntiles) { return (ntiles + kDkScanThreads - 1) / kDkScanThreads; }
 
 __device__ __forceinline__ bool dk_ci_in_use(const unsigned* __restrict__ ci_meta) {
     return ci_meta != nullptr && count_index_in_use(ci_meta);
@@ -90,6 +95,33 @@ TreeGeom tree_geom(int S) {
     g.nodes = off;
     return g;
 }
+
+// The search plan of a table of M keys, from M alone: prepare_table builds the tree from it and both
+// query launchers launch from it (the tuning build's dauc_sort_table_plan reports it).
+struct TablePlan {
+    int k;        // keys per bucket: the smallest power of two with at most kMaxSplit splitters
+    int S;        // splitters = buckets
+    int K;        // the query kernels' template: k where a bucket is read whole (k <= 32), else 0
+    int64_t pad;  // kPadKey keys written past M to fill the last bucket (k <= 32; larger buckets are
+                  // binary-searched with bounds: k - 1 < 64 keys of slack in the sort workspace)
+    TreeGeom g;
+    size_t lds;   // the query kernels' dynamic LDS: the stored tree
+};
+
+TablePlan table_plan(int64_t M) {
+    TablePlan p{};
+    p.k = 1;
+    while ((M + p.k - 1) / p.k > kMaxSplit) p.k *= 2;
+    p.S = static_cast<int>((M + p.k - 1) / p.k);
+    p.K = p.k <= 32 ? p.k : 0;
+    p.pad = p.K ? int64_t(p.S) * p.k - M : 0;
+    p.g = tree_geom(p.S);
+    p.lds = size_t(p.g.nodes) * sizeof(TreeNode);
+    return p;
+}
+
+// the largest table the count index is built for (1.5 keys per cell at most)
+constexpr int64_t kCiMaxTable = 3 * int64_t(kCiMaxCells) / 2;
 
 __device__ __forceinline__ void store_node(uint4* t, int64_t c, const unsigned (&k)[4]) { t[c] = uint4{k[0], k[1], k[2], k[3]}; }
 
@@ -788,7 +820,7 @@ __global__ __launch_bounds__(kDkScanThreads) void dk_scan_kernel(const unsigned*
                                                                  int64_t ntiles) {
     if (dk_ci_in_use(ci_meta)) return;
     __shared__ unsigned wtot[kDkScanThreads / kWave];
-    const int64_t per = (ntiles + kDkScanThreads - 1) / kDkScanThreads;
+    const int64_t per = dk_scan_run(ntiles);
     const int64_t t0 = int64_t(threadIdx.x) * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
     unsigned long long mine = 0;
     for (int64_t t = t0; t < t1; ++t) mine += dk.tcnt[t];
@@ -1139,14 +1171,13 @@ static_assert(kDkQueryLds + 3 * (kQueryThreads / kWave) * 8 <= 160 * 1024, "the 
 static_assert(kDkQueryLdsSmall + 3 * (kQueryThreads / kWave) * 8 <= 160 * 1024, "the distinct-key query's LDS");
 
 template <bool TABLE_POS>
-int launch_query(int k, const float* q, int64_t L, const TreeNode* tree, const TreeGeom& g, const unsigned* sorted,
+int launch_query(const TablePlan& p, const float* q, int64_t L, const TreeNode* tree, const unsigned* sorted,
                  int64_t M, unsigned long long* out, hipStream_t st, const unsigned* dk_meta = nullptr) {
     const dim3 grid(query_grid(L)), block(kQueryThreads);
-    const size_t lds = size_t(g.nodes) * sizeof(TreeNode);
-#define DAUC_QC(KV) \
-    hipLaunchKernelGGL((query_count_kernel<KV, TABLE_POS>), grid, block, lds, st, q, L, tree, g, k, sorted, M, out, \
-                       dk_meta)
-    switch (k) {
+#define DAUC_QC(KV)                                                                                              \
+    hipLaunchKernelGGL((query_count_kernel<KV, TABLE_POS>), grid, block, p.lds, st, q, L, tree, p.g, p.k, sorted, M, \
+                       out, dk_meta)
+    switch (p.K) {
         case 1: DAUC_QC(1); break;
         case 2: DAUC_QC(2); break;
         case 4: DAUC_QC(4); break;
@@ -1209,15 +1240,14 @@ int launch_dk(const LabeledQueries& q, const LT* lab, const unsigned* ci_meta, c
 }
 
 template <typename LT>
-int launch_labeled(int k, const LabeledQueries& q, const LT* lab, const TreeNode* tree, const TreeGeom& g,
+int launch_labeled(const TablePlan& p, const LabeledQueries& q, const LT* lab, const TreeNode* tree,
                    const unsigned* sorted, int64_t M, const unsigned* meta, hipStream_t st,
                    const unsigned* dk_meta = nullptr) {
     const dim3 grid(query_grid(q.end - q.begin)), block(kQueryThreads);
-    const size_t lds = size_t(g.nodes) * sizeof(TreeNode);
-#define DAUC_QL(KV)                                                                                                 \
-    hipLaunchKernelGGL((query_labeled_kernel<KV, LT>), grid, block, lds, st, q.scores, lab, q.begin, q.end, tree, g, \
-                       k, sorted, M, q.wins_ties, q.nonfinite, meta, dk_meta)
-    switch (k) {
+#define DAUC_QL(KV)                                                                                              \
+    hipLaunchKernelGGL((query_labeled_kernel<KV, LT>), grid, block, p.lds, st, q.scores, lab, q.begin, q.end, tree, \
+                       p.g, p.k, sorted, M, q.wins_ties, q.nonfinite, meta, dk_meta)
+    switch (p.K) {
         case 1: DAUC_QL(1); break;
         case 2: DAUC_QL(2); break;
         case 4: DAUC_QL(4); break;
@@ -1230,26 +1260,17 @@ int launch_labeled(int k, const LabeledQueries& q, const LT* lab, const TreeNode
     return launch_status();
 }
 
-// sort the table, build the tree; returns the tree pointer and geometry
-int prepare_table(const float* table, int64_t M, const SortWorkspace& ws, hipStream_t st, const unsigned** sorted,
-                  int* k_out, TreeGeom* g_out, unsigned* ci_first = nullptr) {
+// sort the table, build the tree of its plan (table_plan(M)) into ws.tree
+int prepare_table(const float* table, int64_t M, const TablePlan& p, const SortWorkspace& ws, hipStream_t st,
+                  const unsigned** sorted, unsigned* ci_first = nullptr) {
     int rc = radix_sort_keys(table, M, ws.sort, st, sorted);
     if (rc) return rc;
-    int k = 1;
-    while ((M + k - 1) / k > kMaxSplit) k *= 2;
-    const int S = static_cast<int>((M + k - 1) / k);
-    const TreeGeom g = tree_geom(S);
-    // buckets of <= 32 keys are read whole (one vector load), so their tail is padded; larger
-    // ones are binary-searched with bounds (k - 1 < 64 keys of slack in the sort workspace)
-    const int64_t pad = k <= 32 ? int64_t(S) * k - M : 0;
     const int n_first = ci_first ? kCiTop : 0;
-    int64_t nthreads = (g.nodes > pad) ? g.nodes : pad;
+    int64_t nthreads = (p.g.nodes > p.pad) ? p.g.nodes : p.pad;
     if (nthreads < 8) nthreads = 8;
     if (nthreads < n_first) nthreads = n_first;
     hipLaunchKernelGGL(build_tree_kernel, dim3(static_cast<unsigned>((nthreads + 255) / 256)), dim3(256), 0, st,
-                       const_cast<unsigned*>(*sorted), M, pad, k, g, ws.tree, ci_first, n_first);
-    *k_out = k;
-    *g_out = g;
+                       const_cast<unsigned*>(*sorted), M, p.pad, p.k, p.g, ws.tree, ci_first, n_first);
     return launch_status();
 }
 
@@ -1264,23 +1285,22 @@ int counts_sorted_labeled(const float* pos, int64_t P, const LabeledQueries& q, 
     if (workspace == nullptr || workspace_bytes < dauc_sort_workspace_size(P) || P > 0xffffffffLL) return DAUC_EINVAL;
     const SortWorkspace ws = sort_workspace(workspace, P);
     const unsigned* sorted = nullptr;
-    int k = 1;
-    TreeGeom g{};
+    const TablePlan plan = table_plan(P);
     // the search structure: mode 0 the count index where the table can use it, else the
     // distinct-key index where it holds the table, else the tree (every choice made on the device);
     // 1 the tree; 2 the distinct-key index, else the tree
     const int mode = g_search_mode;
-    const bool count = count_index && mode == 0 && 2 * P <= 3 * int64_t(kCiMaxCells);
+    const bool count = count_index && mode == 0 && P <= kCiMaxTable;
     const bool distinct = mode == 0 || mode == 2;  // the distinct-key index where the count index is not used
     const CountWs& nw = ws.count;
     const DkWs& dk = ws.dk;
-    int rc = prepare_table(pos, P, ws, st, &sorted, &k, &g, count ? nw.first : nullptr);
+    int rc = prepare_table(pos, P, plan, ws, st, &sorted, count ? nw.first : nullptr);
     if (rc) return rc;
     if (count && (rc = prepare_count(sorted, P, nw, st))) return rc;
     const unsigned* meta = count ? nw.meta : nullptr;
     if (distinct && (rc = prepare_dk(sorted, P, meta, dk, st))) return rc;
     rc = with_labels(q.labels, q.label_dtype, [&](auto* lab) {
-        return launch_labeled(k, q, lab, ws.tree, g, sorted, P, meta, st, distinct ? dk.meta : nullptr);
+        return launch_labeled(plan, q, lab, ws.tree, sorted, P, meta, st, distinct ? dk.meta : nullptr);
     });
     if (rc == DAUC_OK && count) rc = launch_ci(q, nw, sorted, P, st, CiForm::sorted());
     if (rc == DAUC_OK && distinct)
@@ -1302,6 +1322,33 @@ int dauc_set_search_mode(int mode) {
     g_search_mode = mode;
     return DAUC_OK;
 }
+
+// tuning builds: the plan of the sorted path for a table of M keys (include/dauc_tuning.h), from the
+// functions the launchers launch from (sort_layout, table_plan, dk_tiles) and the run lengths the
+// two one-workgroup scans compute from them; host arithmetic only
+int dauc_sort_table_plan(int64_t M, int64_t out[DAUC_SORT_PLAN_WORDS]) {
+    if (out == nullptr || M < 1 || M > 0xffffffffLL) return DAUC_EINVAL;
+    WsWalker w(nullptr);
+    const SortWs s = sort_layout(w, M);
+    const TablePlan p = table_plan(M);
+    out[0] = s.ntiles;
+    out[1] = s.fused_scan ? 0 : 1;
+    out[2] = s.nsum;
+    out[3] = scan_sums_run(s.nsum);
+    out[4] = p.k;
+    out[5] = p.S;
+    out[6] = p.g.H;
+    out[7] = p.g.nodes;
+    out[8] = static_cast<int64_t>(p.lds);
+    out[9] = p.pad;
+    out[10] = p.K;
+    out[11] = dk_tiles(M);
+    out[12] = dk_scan_run(dk_tiles(M));
+    out[13] = kDkMax;
+    out[14] = kCiMaxTable;
+    out[15] = kMaxSplit;
+    return DAUC_OK;
+}
 #endif
 
 int dauc_auc_counts_sorted(const float* pos, int64_t P, const float* neg, int64_t N,
@@ -1319,9 +1366,8 @@ int dauc_auc_counts_sorted(const float* pos, int64_t P, const float* neg, int64_
     const SortWorkspace ws = sort_workspace(workspace, M);
     const TreeNode* tree = ws.tree;
     const unsigned* sorted = nullptr;
-    int k = 1;
-    TreeGeom g{};
-    int rc = prepare_table(table_pos ? pos : neg, M, ws, st, &sorted, &k, &g);
+    const TablePlan plan = table_plan(M);
+    int rc = prepare_table(table_pos ? pos : neg, M, plan, ws, st, &sorted);
     if (rc) return rc;
     const float* q = table_pos ? neg : pos;
     // the distinct-key index where it holds the table (tie-heavy), else the tree: chosen on the device
@@ -1329,8 +1375,8 @@ int dauc_auc_counts_sorted(const float* pos, int64_t P, const float* neg, int64_
     const DkWs& dk = ws.dk;
     if (distinct && (rc = prepare_dk(sorted, M, nullptr, dk, st))) return rc;
     const unsigned* dkm = distinct ? dk.meta : nullptr;
-    rc = table_pos ? launch_query<true>(k, q, L, tree, g, sorted, M, wins_ties, st, dkm)
-                   : launch_query<false>(k, q, L, tree, g, sorted, M, wins_ties, st, dkm);
+    rc = table_pos ? launch_query<true>(plan, q, L, tree, sorted, M, wins_ties, st, dkm)
+                   : launch_query<false>(plan, q, L, tree, sorted, M, wins_ties, st, dkm);
     if (rc || !distinct) return rc;
     return table_pos ? launch_dk_plain<true>(q, L, dk, M, wins_ties, st)
                      : launch_dk_plain<false>(q, L, dk, M, wins_ties, st);

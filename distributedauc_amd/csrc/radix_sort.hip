@@ -4,7 +4,7 @@
 // Sort (per 8-bit digit, 4 passes, keys only; 2048-key tiles, one 256-thread workgroup each):
 //   hist    : LDS histogram of the tile's digit -> hist[digit][tile] (digit-major)
 //   scan    : small sorts (<= 256 tiles) have none — every scatter workgroup derives its own
-//             offsets from the raw histogram; larger sorts scan it in 1 or 3 launches
+//             offsets from the raw histogram; larger sorts scan it in 3 launches
 //   scatter : wave w owns the tile's keys [512w, 512w + 512); a key's stable rank among its
 //             wave's keys with the same digit = the wave's running count of that digit (a
 //             wave-private LDS row) + the same-digit lanes below it (8 ballots); one barrier turns
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kScanBlock) void scan_blocks_kernel(unsigned* __res
 __global__ __launch_bounds__(kScanBlock) void scan_sums_kernel(unsigned* __restrict__ sums, int64_t nb) {
     // one block: exclusive scan of nb block sums (nb <= kScanBlock * per-thread run)
     __shared__ unsigned s[kScanBlock];
-    const int64_t per = (nb + kScanBlock - 1) / kScanBlock;
+    const int64_t per = scan_sums_run(nb);
     const int64_t b0 = int64_t(threadIdx.x) * per;
     const int64_t b1 = (b0 + per < nb) ? b0 + per : nb;
     unsigned local = 0;
@@ -88,8 +88,7 @@ __global__ __launch_bounds__(kScanBlock) void scan_add_kernel(unsigned* __restri
 
 // FUSED_SCAN: offs is the raw digit-major histogram; every workgroup derives its own output
 // offsets from it (its digit's count in the tiles before it + the exclusive scan of the digit
-// totals): a small sort (<= kFusedScanTiles tiles) then needs no scan launches at all.
-constexpr int64_t kFusedScanTiles = 256;
+// totals): a small sort (<= kFusedScanTiles tiles, sort_workspace.h) then needs no scan launches at all.
 
 // exclusive scan of v over the block's 256 threads (thread t holds digit t): wave scans by
 // shuffles, then the wave totals through LDS (one barrier); returns the exclusive prefix
@@ -213,7 +212,7 @@ int radix_sort_keys(const float* neg, int64_t N, const SortWs& w, hipStream_t st
             hipLaunchKernelGGL(radix_hist_kernel<false>, dim3(w.ntiles), dim3(kSortThreads), 0, st,
                                static_cast<const void*>(src), N, shift, w.hist, w.ntiles);
         const void* in = pass == 0 ? static_cast<const void*>(neg) : static_cast<const void*>(src);
-        if (w.ntiles <= kFusedScanTiles) {
+        if (w.fused_scan) {
             // small sorts are launch-bound: the scatter workgroups scan the histogram themselves
             if (pass == 0)
                 hipLaunchKernelGGL((radix_scatter_kernel<true, true>), dim3(w.ntiles), dim3(kSortThreads), 0, st,
@@ -222,13 +221,9 @@ int radix_sort_keys(const float* neg, int64_t N, const SortWs& w, hipStream_t st
                 hipLaunchKernelGGL((radix_scatter_kernel<false, true>), dim3(w.ntiles), dim3(kSortThreads), 0, st,
                                    in, N, shift, w.hist, w.ntiles, dst);
         } else {
-            if (w.m <= kSingleScan) {
-                hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanBlock), 0, st, w.hist, w.m);
-            } else {
-                hipLaunchKernelGGL(scan_blocks_kernel, dim3(w.nsum), dim3(kScanBlock), 0, st, w.hist, w.m, w.sums);
-                hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanBlock), 0, st, w.sums, w.nsum);
-                hipLaunchKernelGGL(scan_add_kernel, dim3(w.nsum), dim3(kScanBlock), 0, st, w.hist, w.m, w.sums);
-            }
+            hipLaunchKernelGGL(scan_blocks_kernel, dim3(w.nsum), dim3(kScanBlock), 0, st, w.hist, w.m, w.sums);
+            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanBlock), 0, st, w.sums, w.nsum);
+            hipLaunchKernelGGL(scan_add_kernel, dim3(w.nsum), dim3(kScanBlock), 0, st, w.hist, w.m, w.sums);
             if (pass == 0)
                 hipLaunchKernelGGL((radix_scatter_kernel<true, false>), dim3(w.ntiles), dim3(kSortThreads), 0, st,
                                    in, N, shift, w.hist, w.ntiles, dst);

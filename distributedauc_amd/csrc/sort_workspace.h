@@ -29,16 +29,26 @@ constexpr int kPerThread = 8;  // keys per thread per pass tile
 constexpr int kTile = kSortThreads * kPerThread;  // 2048 keys (8 per thread: the hist pass 4.9 vs 6.1 us at 134k keys)
 constexpr int kRadix = 256;
 constexpr int kScanBlock = 1024;
-constexpr int64_t kSingleScan = 32768;  // histogram entries one workgroup scans alone (<= 512K keys)
+// A sort of up to kFusedScanTiles tiles has no scan launches: every scatter workgroup derives its own
+// offsets from the raw histogram (radix_sort.hip, radix_scatter_kernel<., true>); a larger one scans
+// the histogram in three launches (blocks, block sums, add back).
+constexpr int64_t kFusedScanTiles = 256;
 
 inline int64_t tiles_for(int64_t n) { return (n + kTile - 1) / kTile; }
 
+// block sums each thread of the one-workgroup scan_sums_kernel takes (its run loop: 2 or more from
+// 1025 block sums on, i.e. more than 4096 tiles)
+__host__ __device__ inline int64_t scan_sums_run(int64_t nb) { return (nb + kScanBlock - 1) / kScanBlock; }
+
+// The sort's plan and buffers: radix_sort_keys launches from these fields alone, and the tuning
+// build's dauc_sort_table_plan reports them.
 struct SortWs {
     unsigned* keys_a;
     unsigned* keys_b;
     unsigned* hist;
     unsigned* sums;
-    int64_t ntiles, m, nsum;
+    int64_t ntiles, m, nsum;  // tiles; histogram entries (256 per tile); scan blocks of 1024 entries
+    bool fused_scan;          // ntiles <= kFusedScanTiles: no scan launches
 };
 
 inline SortWs sort_layout(WsWalker& w, int64_t n) {
@@ -46,6 +56,7 @@ inline SortWs sort_layout(WsWalker& w, int64_t n) {
     s.ntiles = tiles_for(n);
     s.m = int64_t(kRadix) * s.ntiles;
     s.nsum = (s.m + kScanBlock - 1) / kScanBlock;
+    s.fused_scan = s.ntiles <= kFusedScanTiles;
     s.keys_a = w.take<unsigned>(n + 64);  // + room for the last bucket's kPadKey tail
     s.keys_b = w.take<unsigned>(n + 64);
     s.hist = w.take<unsigned>(s.m);

@@ -129,6 +129,27 @@ int dauc_bn_launch_plan(int64_t M, int C, int dtype, int64_t out[DAUC_BN_PLAN_WO
 int dauc_conv3x3_wgrad_launch_plan(int64_t N, int H, int W, int Ci, int Ho, int Wo, int Co, int stride,
                                    int64_t out[DAUC_WGRAD_PLAN_WORDS]);
 
+/* The plan of the sorted exact-AUC path (dauc_auc_counts_sorted / _sorted_labeled; csrc/radix_sort.hip,
+ * csrc/auc_sort.hip) for a table of M keys (the smaller class), from the functions its launchers
+ * launch from (sort_layout, table_plan, dk_tiles); host arithmetic only, no GPU is touched. For the
+ * tests: they derive from it which scan form the sort runs, which instantiation of the tree kernels
+ * (query_count_kernel<K, .> / query_labeled_kernel<K, .>) counts, and how long the runs of the two
+ * one-workgroup scans are, so that a retune of the splitter cap or the tile sizes cannot leave a
+ * kernel untested. out[0..15]:
+ *   0 sort tiles (2048 keys each)     1 scan form: 0 fused into the scatter, 1 three launches
+ *   2 nsum, scan blocks (1024 histogram entries each; launched in form 1 only)
+ *   3 block sums per scan_sums_kernel thread (its run loop: >= 2 past 1024 block sums)
+ *   4 k, keys per bucket              5 S, splitters = buckets         6 H, tree height
+ *   7 stored tree nodes (one padding node per level included)          8 the query's dynamic LDS bytes
+ *   9 pad keys written past M (k <= 32: the last bucket is read whole; 0 for larger buckets)
+ *  10 K, the kernels' template: k if k <= 32, else 0 (buckets finished by binary searches)
+ *  11 distinct-key tiles (1024 keys) 12 tiles per dk_scan_kernel thread
+ *  13 kDkMax, the most distinct keys the distinct-key index holds (more: the tree counts)
+ *  14 the largest table the count index is built for                  15 kMaxSplit, the cap on S
+ * DAUC_EINVAL for M < 1 or M > 0xffffffff (the entry points refuse such tables). */
+#define DAUC_SORT_PLAN_WORDS 16
+int dauc_sort_table_plan(int64_t M, int64_t out[DAUC_SORT_PLAN_WORDS]);
+
 #ifdef __cplusplus
 }
 #endif

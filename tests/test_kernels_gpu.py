@@ -1145,10 +1145,13 @@ def test_sorted_counts_match_pair_count(dev, P, N):
                                             (400_000, 1_000_000, True), (600_000, 700_000, True),
                                             (700_000, 600_000, False), (1_100_000, 1_300_000, True)])
 def test_sorted_counts_bucket_sizes(dev, M, L, table_pos):
-    """The search tree holds every k-th key of the sorted smaller class (<= 32767 splitters, so
-    these sizes give k = 1, 2, 4, 8, 16, 32 (one bucket load) and 64 (k > 32: binary search in
-    global memory)). Every k, and both table sides, vs the pair-count
-    kernel on tie-heavy scores (ties at splitter boundaries included), bit-exact."""
+    """The distinct-key index at table sizes from 10,000 to 1,100,000 keys, both table sides, vs the
+    pair-count kernel, bit-exact. The scores lie on 5003 grid values, so every table holds at most
+    5004 distinct keys: the distinct-key index counts (dk_plain_kernel) and the tree kernel, built for
+    k = 1 .. 32 at these sizes, returns on its first line. What this reaches: the mark / scan / write
+    passes over 10 .. 1075 tiles of 1024 keys -- two tiles per dk_scan_kernel thread at 1,100,000 --
+    and, from 600,000 keys on, the sort's three-launch scan. The tree itself is walked at every k by
+    tests/test_auc_tree_gpu.py."""
     from distributedauc_amd import ops
 
     rng = np.random.default_rng(M + L)
